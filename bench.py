@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- training rays/s of the NoPe-NeRF render hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 starts itself: without WORLD_SIZE in the environment the script re-executes under `python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU, RCCL); launched by torchrun it reads
@@ -17,9 +17,17 @@ Headline workload = BASELINE.json configs[1]: 1024 rays x (64+128) samples per G
 learnable, fp32.  The reference has no coarse/fine resampling (SURVEY.md header), so "64 coarse + 128 fine" is pinned as 192
 stratified samples per ray in a single pass.  Weak scaling: every rank renders its own shard of a (rays_per_gpu * N)-ray step.
 
-The ONE JSON line carries
-  * `roofline`      -- the dominant fused-MLP kernel timed with HIP events on the launch stream; algorithmic FLOPs =
-                       1 186 816 per sample per pass (BASELINE.md section 2);
+A plain run sets up, warms up, times K steps and prints ONE JSON line with the headline figure (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the per-step spread `step_ms`, the workload `config`, `final_loss`).
+`--dump-outputs DIR` then writes what the last timed step computed as DIR/<name>.npy (float32): the scalars of the loss dict
+Trainer.train_step returned (`loss.<key>`) and every parameter of the field, pose and distortion networks after its Adam
+updates (`param.<net>.<name>`); the inputs are seeded, so two builds given the same arguments can be compared array by array.
+
+`--full` adds everything else the benchmark measures, each of which costs time of its own:
+  * `collective`    -- (N > 1 or NNR_BENCH_FORCE_DIST=1) the step's all-reduce timed on its own;
+  * `roofline`      -- the dominant fused-MLP kernel timed with HIP events on the launch stream (the timed steps then also record
+                       every MLP kernel launch: nnr_prof_begin / _end); algorithmic FLOPs = 1 186 816 per sample per pass
+                       (BASELINE.md section 2);
   * `cpu_baseline`  -- the CPU oracle (a port of the reference's PyTorch path) timed on this host's cores on a bounded
                        sample of the same workload (2 warm-ups + 5 timed steps);
   * `configs`       -- (N = 1 only) the other BASELINE.json configurations measured in the same run: `bf16_4096x128`
@@ -522,45 +530,10 @@ def _host_cpu():
     return os.cpu_count() or 1, model
 
 
-def cpu_baseline_reference(rays=R_PER_GPU, warmup=2, steps=5):
-    """The REFERENCE ITSELF on this host's cores (`kind: "reference"`): tools/cpu_reference_baseline.py, in its own process, runs the
-    staged, unmodified copy of /root/reference/model (gpurun_stage/reference_cpu/, git-ignored, put there by tools/stage_reference.py /
-    __graft_entry__.build() in the authoring container) -- nope_nerf.forward + the reference's loss heads + backward on the headline
-    workload, 2 warm-ups + 5 timed steps, median.  None when nothing is staged or the worker fails (the caller falls back to the port)."""
-    stage = os.path.join(ROOT, 'gpurun_stage', 'reference_cpu')
-    if not os.path.isfile(os.path.join(stage, 'model', 'rendering.py')):
-        return None, 'no staged reference (gpurun_stage/reference_cpu/model missing)'
-    cmd = [sys.executable, os.path.join(ROOT, 'tools', 'cpu_reference_baseline.py'), '--rays', str(rays), '--samples', str(N_SAMPLES),
-           '--hidden', str(HIDDEN), '--warmup', str(warmup), '--steps', str(steps)]
-    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'PYTHONPATH')}
-    try:
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
-        lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
-        if r.returncode != 0 or not lines:
-            return None, 'reference worker failed: ' + (r.stderr.strip().splitlines() or ['?'])[-1][:300]
-        return json.loads(lines[-1]), None
-    except Exception as e:        # noqa: BLE001 -- a baseline must never take the benchmark down
-        return None, 'reference worker failed: %r' % (e,)
-
-
-def cpu_baseline(sample_rays=192, warmup=2, steps=5):
-    """`cpu_baseline` of the JSON line: the reference's own code when it is staged (cpu_baseline_reference: kind "reference", the
-    whole 1024-ray headline step), otherwise the oracle port on a bounded sample (cpu_baseline_port: kind "port"); the block says
-    which ran and, for the port, why."""
-    ref, why = cpu_baseline_reference()
-    if ref is not None:
-        port = cpu_baseline_port(sample_rays, warmup, steps)      # the oracle beside it: the port runs at the reference's speed
-        ref['oracle_port_cross_check'] = {k: port[k] for k in ('value', 'unit', 'sample')}
-        return ref
-    out = cpu_baseline_port(sample_rays, warmup, steps)
-    out['fallback_reason'] = why
-    return out
-
-
 def cpu_baseline_port(sample_rays=192, warmup=2, steps=5):
-    """The CPU oracle (oracle/nerf_oracle.py, a port of the reference's PyTorch path: the reference itself cannot travel to the GPU
-    box) on this host's cores, on a bounded sample of the headline workload: `sample_rays` rays x 192 samples, D=256, forward +
-    loss heads + backward; median of `steps` timed steps after `warmup` untimed ones."""
+    """`cpu_baseline` of the JSON line: the CPU oracle (oracle/nerf_oracle.py, a port of the reference's PyTorch path) on this host's
+    cores, on a bounded sample of the headline workload: `sample_rays` rays x 192 samples, D=256, forward + loss heads + backward;
+    median of `steps` timed steps after `warmup` untimed ones."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import nerf_oracle as orc
     host_cores, cpu_model = _host_cpu()
@@ -594,35 +567,11 @@ def cpu_baseline_port(sample_rays=192, warmup=2, steps=5):
                       f'warm-ups, torch {torch.__version__} CPU, {threads} threads on a {host_cores}-core host'}
 
 
-def cpu_config0(warmup=1, steps=3):
-    """BASELINE configs[0] -- the reference's own CPU-runnable case -- on the REFERENCE ITSELF when it is staged (`kind: "reference"`):
-    tools/cpu_reference_baseline.py --train-step runs the staged, unmodified /root/reference/model package's `Trainer.train_step`
-    (model/training.py:67-97) with configs/Tanks/Ignatius.yaml over configs/default.yaml, 32 rays x 64 samples, hidden_dim 128, the
-    first-phase per-image losses on, three Adam steps, for a small sweep of thread counts (2 k samples per step do not feed 32 threads) and
-    reports the best; otherwise the oracle port (`kind: "port"`, with the reason)."""
-    stage = os.path.join(ROOT, 'gpurun_stage', 'reference_cpu')
-    why = 'no staged reference (gpurun_stage/reference_cpu/model missing)'
-    if os.path.isfile(os.path.join(stage, 'model', 'training.py')) and os.path.isfile(os.path.join(stage, 'configs', 'Tanks', 'Ignatius.yaml')):
-        cmd = [sys.executable, os.path.join(ROOT, 'tools', 'cpu_reference_baseline.py'), '--train-step', '--rays', '32', '--samples', '64',
-               '--hidden', '128', '--warmup', str(warmup), '--steps', str(steps)]
-        env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'PYTHONPATH')}
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
-            lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
-            if r.returncode == 0 and lines:
-                return json.loads(lines[-1])
-            why = 'reference worker failed: ' + (r.stderr.strip().splitlines() or ['?'])[-1][:300]
-        except Exception as e:        # noqa: BLE001 -- a baseline must never take the benchmark down
-            why = 'reference worker failed: %r' % (e,)
-    out = cpu_config0_port(warmup, steps)
-    out['fallback_reason'] = why
-    return out
-
-
 def cpu_config0_port(warmup=1, steps=3, threads=None):
-    """The same case through the oracle port (fallback when no reference is staged): forward + backward of the render slice and the
-    per-image terms on 108 x 192 mono-depth maps (a 27 x 48 grid).  threads=None: the thread counts the reference path sweeps (1, 2, 4, 8,
-    min(cores, 32)) are each timed and the FASTEST is reported, with its thread count -- a slow baseline flatters every ratio built on it."""
+    """`configs.cpu_32x64_d128`: BASELINE configs[0] -- the reference's own CPU-runnable case (configs/Tanks/Ignatius.yaml settings, 32 rays
+    x 64 samples, hidden_dim 128, the first-phase per-image losses on) -- through the oracle port: forward + backward of the render slice
+    and the per-image terms on 108 x 192 mono-depth maps (a 27 x 48 grid).  threads=None: the thread counts (1, 2, 4, 8, min(cores, 32))
+    are each timed and the FASTEST is reported, with its thread count -- a slow baseline flatters every ratio built on it."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import nerf_oracle as orc
     host_cores, cpu_model = _host_cpu()
@@ -662,7 +611,9 @@ def cpu_config0_port(warmup=1, steps=3, threads=None):
             'sample': f'median of {steps} steps after {warmup} warm-ups'}
 
 
-def _timed_steps(trainer, data, warmup, steps, use_dist):
+def _timed_steps(trainer, data, warmup, steps, use_dist, per_kernel=True, last=None):
+    """Warm up, then time `steps` training steps: (elapsed seconds, final loss, in_step).  in_step holds the per-step spread and, with
+    `per_kernel`, the mean durations of the three MLP kernels inside the timed steps; `last` (a dict) receives the last step's loss dict."""
     def step(i):
         return trainer.train_step(data, it=i, epoch=0, scheduling_start=10000, render_path=None)
     ld = None
@@ -673,7 +624,8 @@ def _timed_steps(trainer, data, warmup, steps, use_dist):
     torch.cuda.synchronize()
     from nnr import lib as L
     lib = L.load()
-    L.check(lib.nnr_prof_begin(steps), 'nnr_prof_begin')      # two event records per MLP kernel launch: microseconds of host time per step
+    if per_kernel:
+        L.check(lib.nnr_prof_begin(steps), 'nnr_prof_begin')      # two event records per MLP kernel launch: microseconds of host time per step
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]      # one record per step on the step's stream, no sync:
     t0 = time.perf_counter()                                                      # the spread of the timed steps (the region is ~70 ms)
     marks[0].record()
@@ -685,9 +637,11 @@ def _timed_steps(trainer, data, warmup, steps, use_dist):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    ms4, n4 = (C.c_float * 4)(), (C.c_int32 * 4)()
-    L.check(lib.nnr_prof_end(ms4, n4), 'nnr_prof_end')
-    in_step = {'mlp_fwd': float(ms4[0]), 'mlp_dgrad': float(ms4[1]), 'mlp_wgrad': float(ms4[2]), 'launches': int(n4[0])}
+    in_step = {}
+    if per_kernel:
+        ms4, n4 = (C.c_float * 4)(), (C.c_int32 * 4)()
+        L.check(lib.nnr_prof_end(ms4, n4), 'nnr_prof_end')
+        in_step = {'mlp_fwd': float(ms4[0]), 'mlp_dgrad': float(ms4[1]), 'mlp_wgrad': float(ms4[2]), 'launches': int(n4[0])}
     per_step = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(steps)], dtype=np.float64)
     in_step['step_ms'] = {'mean': round(float(per_step.mean()), 4), 'std': round(float(per_step.std()), 4), 'min': round(float(per_step.min()), 4),
                           'max': round(float(per_step.max()), 4), 'median': round(float(np.median(per_step)), 4),
@@ -697,7 +651,28 @@ def _timed_steps(trainer, data, warmup, steps, use_dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     trainer.flush_nan_check()
+    if last is not None:
+        last['loss_dict'] = ld
     return elapsed, float(ld['loss'].detach()), in_step
+
+
+def dump_outputs(out_dir, trainer, loss_dict):
+    """--dump-outputs: what the last timed step computed, as <out_dir>/<name>.npy in float32 -- the scalars of its loss dict and every
+    parameter of the three networks after the step's Adam updates (about 2.4 MB at D = 256)."""
+    arrays = {}
+    for k, v in loss_dict.items():
+        if torch.is_tensor(v):
+            arrays['loss.' + k] = v.detach().as_subclass(torch.Tensor).float().cpu().numpy()
+        elif isinstance(v, (int, float)):
+            arrays['loss.' + k] = np.asarray(v, dtype=np.float32)
+    for tag, net in (('model', trainer.model), ('pose', trainer.pose_param_net), ('distortion', trainer.distortion_net)):
+        for name, p in net.named_parameters():
+            arrays['param.%s.%s' % (tag, name)] = p.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes, more than 64 MB"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def extra_config(device, name, rays, n_samples, bf16, steps=10, warmup=3, products=None, aux=False):
@@ -801,6 +776,11 @@ def main():
                     help='bf16-MFMA mode of the MLP kernels for the MAIN measurement (BASELINE configs[2] arithmetic; not the headline metric)')
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / rendezvous check without a GPU: every rank joins a gloo group, all-reduces and rank 0 prints the line skeleton')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the last step\'s loss scalars and updated parameters to DIR/<name>.npy (float32)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: in-step kernel times + roofline, clock and HBM probes, the collective '
+                         'probe, the CPU baselines and the extra `configs` blocks (--no-cpu-baseline / --no-extra trim it)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -855,9 +835,12 @@ def main():
         R = args.total_rays // world
     trainer, net = build_trainer(device, world, args.aux, args.bf16, R, N)
     data = synthetic_batch(device)
-    elapsed, loss_val, in_step = _timed_steps(trainer, data, args.warmup, args.steps, use_dist)
+    last = {}
+    elapsed, loss_val, in_step = _timed_steps(trainer, data, args.warmup, args.steps, use_dist, per_kernel=args.full, last=last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, last['loss_dict'])
     ranks_seen, ar_us = (1, None)
-    if use_dist:
+    if use_dist and args.full:
         n_grad = sum(p.numel() for m in (net, trainer.pose_param_net, trainer.distortion_net) for p in m.parameters()) + 9
         ranks_seen, ar_us = allreduce_probe(device, n_grad)
 
@@ -882,6 +865,9 @@ def main():
                        'parallelism': f'dp{world} (ray-sharded, one flat all-reduce)'},
             'final_loss': round(loss_val, 6),
         }
+        if not args.full:
+            print(json.dumps(out), flush=True)
+    if rank == 0 and args.full:      # everything else the benchmark measures, after the headline's own steps
         if use_dist:
             out['collective'] = {'backend': 'rccl' if backend == 'nccl' else 'gloo (shared GPU dry run)', 'rccl_ranks_seen': ranks_seen,
                                  'allreduce_us': round(ar_us, 1), 'bucket_floats': n_grad}
@@ -897,7 +883,7 @@ def main():
             blk['peak_at_measured_clock'] = round(at, 1)
             blk['frac_at_measured_clock'] = round(blk['achieved'] / at, 4)
         out['box'] = box_probe(device)
-        out['cpu_baseline'] = None if (args.no_cpu_baseline or world > 1) else cpu_baseline()
+        out['cpu_baseline'] = None if (args.no_cpu_baseline or world > 1) else cpu_baseline_port()
         if world == 1 and not args.no_extra and headline:
             del trainer
             torch.cuda.empty_cache()
@@ -916,7 +902,7 @@ def main():
                 # point-cloud + surface re-projection losses ON
                 'fp32_1024x192_aux': extra_config(device, 'BASELINE configs[1] in the first training phase: per-image losses (pc + rgb_s) on',
                                                   R_PER_GPU, N_SAMPLES, False, aux=True),
-                'cpu_32x64_d128': None if args.no_cpu_baseline else cpu_config0(),
+                'cpu_32x64_d128': None if args.no_cpu_baseline else cpu_config0_port(),
             }
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "nope-nerf_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 REF = os.environ.get("NNR_REFERENCE", "/root/reference")
 
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "train.py")), reason="reference checkout not present")
+needs_reference = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "train.py")), reason="reference checkout not present")
 
 
 def _free_port():
@@ -66,6 +66,7 @@ def _cfg(data, out_dir):
     }
 
 
+@needs_reference
 def test_unmodified_train_py_under_two_ranks_lands_on_the_single_process_run(tmp_path):
     import scene_writer
     data = str(tmp_path / "data")

@@ -31,7 +31,7 @@ def _run(args, extra_env, launcher=None):
     return json.loads(lines[0])
 
 
-COMMON = ["--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline"]
+COMMON = ["--steps", "3", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline"]      # --full: the collective / roofline blocks
 
 
 def test_two_ranks_share_the_gpu_through_the_real_bench_path():

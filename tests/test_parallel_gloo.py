@@ -13,6 +13,13 @@ import torch.multiprocessing as mp
 import golden_util as gu
 
 
+@pytest.fixture(autouse=True)
+def _restore_render_operator(monkeypatch):
+    """_build swaps the CPU stand-in into nnr.render_rays; where a test calls it in this process, put the HIP operator back afterwards."""
+    from model import rendering
+    monkeypatch.setattr(rendering.nnr, "render_rays", rendering.nnr.render_rays)
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
