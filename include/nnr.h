@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define NNR_ABI_VERSION 6
+#define NNR_ABI_VERSION 7
 
 /* error codes */
 #define NNR_OK 0
@@ -150,6 +150,18 @@ int64_t nnr_ws_plane(const nnr_cfg* cfg, int plane, int32_t* pitch_out);
  * is [lane = 32 h + c][4 floats] = features 8 j + 4 h + {0..3} of sample 32 chunk + c (nnr_layout.h: tile32_index); offset and pitch
  * (= floats per sample) are those nnr_ws_plane reports.  <0 for an unknown plane. */
 int nnr_ws_plane_layout(const nnr_cfg* cfg, int plane);
+
+/* The phong geometry renderer's depth search (reference model/rendering.py:277-418, ray_marching + secant; model/rendering.py here).
+ * cfg: n_rays = R, n_samples = n_steps in [2, 1024], hidden 128 / 256, flags NNR_F_SPLIT3 | NNR_F_SPLIT2 (required: the march evaluates in
+ * the two-term fp16 arithmetic, `packed` is that mode's buffer) plus NNR_F_RELU_SIGMA / NNR_F_DIST_ALPHA for the occupancy.
+ * ray_o, ray_d: (R,3) origin and unit direction; t_table: (n_steps) = torch.linspace(0, 1, n_steps); proposals d_j = d_far t_j with d_far the
+ * far root of the ray and the sphere |p| = radius (0 without a root, clamped at 0).  occ = 1 - exp(-softplus(raw)) (relu with
+ * NNR_F_RELU_SIGMA, without the 1 - exp(-.) with NNR_F_DIST_ALPHA), val = occ - 0.5, j* = the first j with val_j val_{j+1} < 0.
+ * A ray hits iff val_0 < 0, j* exists, val_{j*} < 0 and no val is NaN; n_secant secant steps then refine d on [d_{j*}, d_{j*+1}].
+ * d_out (R): the estimate on a hit, +inf on a miss, 0 where val_0 >= 0 (or NaN).  state: (R,4) scratch, 16-byte aligned.
+ * 2 + n_secant launches on `stream`, no host synchronisation.  (ABI 7) */
+int nnr_ray_march(const nnr_cfg* cfg, const float* ray_o, const float* ray_d, float radius, const float* t_table, int32_t n_secant,
+                  const float* packed, float* state, float* d_out, void* stream);
 
 /* Individual stages, exported for profiling and bench.py's per-kernel roofline timing.  Same arguments
  * and workspace contract as the fused entry points above. */

@@ -733,6 +733,26 @@ int nnr_render_fwd(const nnr_cfg* cfg, const float* pts_o, const float* pts_d, c
     return nnr_composite_fwd(cfg, rgb, dist, opt_alpha, opt_z, ws, stream);
 }
 
+// the phong renderer's depth search: one march launch, n_secant secant launches, one launch that writes d (nnr_march_f16.hip)
+int nnr_ray_march(const nnr_cfg* cfg, const float* ray_o, const float* ray_d, float radius, const float* t_table, int32_t n_secant,
+                  const float* packed, float* state, float* d_out, void* stream) {
+    if (!cfg || cfg->n_rays <= 0 || n_secant < 0) return NNR_E_BADCFG;
+    if (cfg->hidden != 128 && cfg->hidden != 256) return NNR_E_UNSUPPORTED;
+    if (cfg->n_samples < 2 || cfg->n_samples > 1024 || (cfg->flags & (NNR_F_TRAIN | NNR_F_WHITE_BG)) || !is_split2(cfg)) return NNR_E_UNSUPPORTED;
+    if (!ray_o || !ray_d || !t_table || !packed || !state || !d_out) return NNR_E_BADCFG;
+    if (!aligned16(packed) || !aligned16(state)) return NNR_E_ALIGN;
+    MarchArgs a{};
+    a.ray_o = ray_o; a.ray_d = ray_d; a.t = t_table; a.packed = packed; a.state = state;
+    a.radius = radius; a.R = cfg->n_rays; a.n_steps = cfg->n_samples;
+    a.flags = cfg->flags & (NNR_F_RELU_SIGMA | NNR_F_DIST_ALPHA);
+    const hipStream_t st = (hipStream_t)stream;
+    hipError_t e = launch_march(cfg->hidden, a, st);
+    a.flat = 1;
+    for (int i = 0; i < n_secant && e == hipSuccess; ++i) e = launch_march(cfg->hidden, a, st);
+    if (e == hipSuccess) e = launch_march_finish(state, d_out, cfg->n_rays, st);
+    return e == hipSuccess ? NNR_OK : hip_fail(e);
+}
+
 int nnr_composite_bwd(const nnr_cfg* cfg, const float* d_rgb, const float* d_dist, float* ws, void* stream) {
     int rc = check_cfg(cfg);
     if (rc != NNR_OK) return rc;

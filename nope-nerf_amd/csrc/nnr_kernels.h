@@ -35,6 +35,19 @@ struct MlpFwdArgs {
                           // wave walks one ray), 0 = flat decomposition
 };
 
+// the phong renderer's occupancy march (nnr_march_f16.hip): ray mode (flat == 0) walks n_steps proposals per ray and writes one state per ray,
+// flat mode (flat == 1) runs one secant step over the states.  state: (R,4) = (d_lo, d_hi, f_lo, f_hi), see the kernel's header for the encoding.
+struct MarchArgs {
+    const float *ray_o, *ray_d;   // (R,3)
+    const float* t;               // (n_steps): torch.linspace(0, 1, n_steps)
+    const float* packed;          // Layout<D, 3> (NNR_F_SPLIT3 | NNR_F_SPLIT2)
+    float* state;                 // (R,4)
+    float radius;
+    int R, n_steps;
+    uint32_t flags;               // NNR_F_RELU_SIGMA / NNR_F_DIST_ALPHA
+    int flat;
+};
+
 struct MlpDgradArgs {
     const float* packed;
     float* ws_dout4;        // (S_pad,4): d rgb_pre[3], d sigma_raw (rows >= S are zero-filled here)
@@ -228,6 +241,8 @@ template <int D, int MODE = 0> hipError_t launch_mlp_dgrad_variant(const MlpDgra
 hipError_t launch_mlp_dgrad(int D, const MlpDgradArgs& a, hipStream_t st, int mode = 0);
 hipError_t launch_mlp_fwd_bf16(int D, const MlpFwdArgs& a, bool train, hipStream_t st);     // nnr_mlp_fwd_bf16.hip
 hipError_t launch_mlp_dgrad_bf16(int D, const MlpDgradArgs& a, hipStream_t st);              // nnr_mlp_dgrad_bf16.hip
+hipError_t launch_march(int D, const MarchArgs& a, hipStream_t st);                              // nnr_march_f16.hip
+hipError_t launch_march_finish(const float* state, float* d_out, int R, hipStream_t st);
 hipError_t launch_composite_fwd(const CompositeArgs& a, hipStream_t st);
 hipError_t launch_composite_bwd(const CompositeArgs& a, hipStream_t st);
 hipError_t launch_ray_reduce(const RayReduceArgs& a, hipStream_t st);

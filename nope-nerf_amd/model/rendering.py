@@ -11,14 +11,16 @@ alpha-compositing, and their backward.
 normal-consistency vector `out['normal']`: second-order autograd through the MLP trunk for the 2 M surface points, in stock torch
 over the same nn.Linear parameters (OfficialStaticNerf.gradient) -- the fused kernels still render.
 
-Not provided (outside the hot path): the phong / ray-marching visualiser
-(`phong_renderer`, `ray_marching`, `secant`); they raise NotImplementedError.
+The phong geometry visualiser (`phong_renderer`, `ray_marching`, `secant`; reference :202-418) runs on the GPU: the occupancy march and
+its secant steps in one HIP kernel (nnr_march_f16.hip via nnr.ops.ray_march), the normals through the training kernels
+(nnr.ops.density_grad), always in the two-term fp16 products.  On CPU tensors they raise NotImplementedError.
 """
 import torch
 import torch.nn as nn
 
 import nnr
 from nnr import camera
+from nnr import ops as _nnr_ops
 from .common import get_ndc_rays_fxfy, pixel_to_world_matrix
 
 epsilon = 1e-6   # the transmittance epsilon of the reference (rendering.py:9) -- applied inside the composite kernel
@@ -216,10 +218,86 @@ class Renderer(nn.Module):
         normals = g[:, 0, :] / (g[:, 0, :].norm(2, dim=1).unsqueeze(-1) + 10 ** (-5))
         return torch.norm(normals[:n] - normals[n:], dim=-1)
 
-    # ------------------------------------------------------------------------------------------------ not on the hot path
-    def phong_renderer(self, *args, **kwargs):
-        raise NotImplementedError("phong_renderer (geometry visualisation, reference rendering.py:202-274) is outside the "
-                                  "HIP hot path; set training.vis_geo: False")
+    # ------------------------------------------------------------------------------------------------ geometry visualisation
+    def _t_table(self, n_steps, device):
+        """torch.linspace(0, 1, n_steps) on the device (reference :327-329: built on the CPU, as there), cached per size.  The first use
+        of a size copies from pinned memory without blocking, so that no call of phong_renderer synchronises with the device."""
+        key = ('t', int(n_steps), str(device))
+        hit = self._z_cache.get(key)
+        if hit is None:
+            hit = torch.linspace(0, 1, steps=n_steps).pin_memory().to(device, non_blocking=True)
+            self._z_cache[key] = hit
+        return hit
 
-    def ray_marching(self, *args, **kwargs):
-        raise NotImplementedError("ray_marching / secant (reference rendering.py:277-418) serve only phong_renderer")
+    def phong_renderer(self, pixels, camera_mat, world_mat, scale_mat, it):
+        """Reference rendering.py:202-273 on the GPU: the depth search (ray_marching), the surface normals -d(raw)/dp / |.| and the
+        diffuse shading with the light at the camera, plus the colour branch at the surface point.  The march runs in
+        nnr_march_f16.hip, the normals through the training kernels (nnr.ops.density_grad), rgb_surf through nnr.ops.mlp_points; all
+        three always use the two-term fp16 products (NNR_F_SPLIT3 | NNR_F_SPLIT2) whatever rendering.mfma_dtype or NNR_FP32_PRODUCTS
+        select for the training step.  No device-to-host synchronisation: every ray is evaluated and masked afterwards.  GPU only."""
+        if not pixels.is_cuda:
+            raise NotImplementedError("phong_renderer runs only on the GPU (HIP march kernel, nnr_march_f16.hip); there is no CPU "
+                                      "geometry renderer -- set training.vis_geo: False for CPU runs")
+        batch_size, num_pixels, _ = pixels.shape
+        if batch_size != 1:
+            raise NotImplementedError("batch size 1 is baked into the reference (rendering.py:86-87); so it is here")
+        rad = self.cfg['radius']
+        net = self.model
+        origin, ray, _, _, _, _ = camera.ray_setup(pixels, None, camera_mat, world_mat, scale_mat, True, True)
+        light = origin[0] / origin[0].norm(2)                                            # camera_world[0,0], normalised (:218-220)
+        self.model.eval()
+        with torch.no_grad():
+            d_i = self.ray_marching(origin.unsqueeze(0), ray.unsqueeze(0), self.model, n_secant_steps=8, n_steps=[512, 513],
+                                    rad=rad)[0]
+            mask_zero = d_i == 0
+            mask_pred = torch.isfinite(d_i)                                              # get_mask (common.py)
+            dists = torch.where(mask_pred, d_i, torch.ones_like(d_i)).masked_fill(mask_zero, 0.)
+            obj = mask_pred & ~mask_zero
+            points = origin + ray * dists.unsqueeze(-1)
+            view = -ray
+            g = _nnr_ops.density_grad(points, net.weights(), net.biases(), net.hidden_dim).neg()   # OfficialStaticNerf.gradient
+            normals = g / g.norm(2, 1, keepdim=True)
+            diffuse = (normals @ light.unsqueeze(1)).clamp_min(0).repeat(1, 3) * 0.7
+            rgb = torch.where(obj.unsqueeze(-1), (0.3 + diffuse).clamp_max(1.0), torch.ones_like(points))
+            rgb_s, _ = _nnr_ops.mlp_points(points, view, net.weights(), net.biases(), hidden=net.hidden_dim, split2=True)
+            rgb_surf = torch.where(obj.unsqueeze(-1), rgb_s, torch.zeros_like(rgb_s))
+        return {'rgb': rgb.reshape(batch_size, -1, 3), 'normal': None, 'rgb_surf': rgb_surf.reshape(batch_size, -1, 3)}
+
+    def ray_marching(self, ray0, ray_direction, model, c=None, tau=0.5, n_steps=[128, 129], n_secant_steps=8,
+                     depth_range=[0., 2.4], max_points=3500000, rad=1.0):
+        """Reference rendering.py:277-386 (+ secant, :388-418) in one call of nnr.ops.ray_march: (B=1, R, 3) origins and unit
+        directions -> d (1, R): the surface depth on a hit, inf on a miss, 0 where the first proposal is occupied.  Proposals from 0
+        (depth_range[0] of the reference, which the CPU reference multiplies by (1 - t)) to the far root of the radius-`rad` sphere;
+        tau is 0.5 as in the reference (which overwrites its argument).  One draw of torch's CPU generator, as the reference makes."""
+        n = int(torch.randint(n_steps[0], n_steps[1], (1,)).item())
+        if not ray0.is_cuda:
+            raise NotImplementedError("ray_marching runs only on the GPU (HIP march kernel, nnr_march_f16.hip)")
+        if ray0.shape[0] != 1:
+            raise NotImplementedError("batch size 1 is baked into the reference (rendering.py:86-87); so it is here")
+        if float(depth_range[0]) != 0.:
+            raise NotImplementedError("the march kernel starts its proposals at 0 (the reference's default and the only value phong uses)")
+        net = model
+        d = _nnr_ops.ray_march(ray0[0], ray_direction[0], self._t_table(n, ray0.device), net.weights(), net.biases(),
+                               hidden=net.hidden_dim, radius=float(rad), n_secant=int(n_secant_steps),
+                               relu_sigma=(net.occ_activation != 'softplus'), dist_alpha=bool(net.dist_alpha))
+        return d.unsqueeze(0)
+
+    def secant(self, f_low, f_high, d_low, d_high, n_secant_steps, ray0_masked, ray_direction_masked, tau, it=0):
+        """Reference rendering.py:388-418 on its own (phong_renderer runs these steps inside the march kernel): the same updates with
+        torch.where instead of boolean-mask assignment, occ from OfficialStaticNerf.forward (the fused kernel on free-standing points).
+        GPU only."""
+        if not ray0_masked.is_cuda:
+            raise NotImplementedError("secant runs only on the GPU (the fused MLP kernel); there is no CPU geometry renderer")
+        d_low, d_high, f_low, f_high = (t.clone() for t in (d_low, d_high, f_low, f_high))
+        d_pred = - f_low * (d_high - d_low) / (f_high - f_low) + d_low
+        for _ in range(n_secant_steps):
+            p_mid = ray0_masked + d_pred.unsqueeze(-1) * ray_direction_masked
+            with torch.no_grad():
+                f_mid = self.model(p_mid, batchwise=False, only_occupancy=True, it=it)[..., 0] - tau
+            ind_low = f_mid < 0
+            d_low = torch.where(ind_low, d_pred, d_low)
+            f_low = torch.where(ind_low, f_mid, f_low)
+            d_high = torch.where(ind_low, d_high, d_pred)
+            f_high = torch.where(ind_low, f_high, f_mid)
+            d_pred = - f_low * (d_high - d_low) / (f_high - f_low) + d_low
+        return d_pred

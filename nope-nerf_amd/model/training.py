@@ -662,12 +662,25 @@ class Trainer(object):
             rgb = torch.cat(rgb, dim=1).view(h, w, 3).cpu().numpy()
             depth = torch.cat(depth, dim=0).view(h, w).cpu().numpy()
         img_out = (rgb * 255).astype(np.uint8)
+        geo = self.vis_geo and pixels.is_cuda
         if not parallel.is_writer():      # data parallel: the frames are identical on every rank, rank 0 writes them
+            if geo:
+                # ... but every rank makes the writer's generator draws (one torch.randint per 1024-pixel chunk in ray_marching): the
+                # DataLoader's shuffle comes from the same generator, and ranks whose generators drifted apart would train on other frames
+                for _ in range((h * w + 1023) // 1024):
+                    torch.randint(512, 513, (1,))
             return img_out
         depth_u8 = np.clip(255.0 / depth.max() * (depth - depth.min()), 0, 255).astype(np.uint8)
         _save_png(depth_u8, os.path.join(out_render_path, '%04d_depth.png' % img_idx))
         Image.fromarray(img_out).convert("RGB").save(os.path.join(out_render_path, '%04d_img.png' % img_idx))
-        if self.vis_geo and not self._warned_geo:
-            logger_py.warning("training.vis_geo: the phong geometry visualiser is outside the HIP hot path; skipping *_geo.png")
+        if geo:      # reference training.py:144-160: the phong geometry frame, 1024 pixels per call
+            with torch.no_grad():
+                geo_rgb = [self.model(pix_i, None, camera_mat, world_mat, scale_mat, 'phong_renderer', add_noise=False, eval_mode=True,
+                                      it=it, depth_img=dpt, img_size=(h, w))['rgb'] for pix_i in torch.split(pixels, 1024, dim=1)]
+                geo_rgb = torch.cat(geo_rgb, dim=1).view(h, w, 3).cpu().numpy()
+            img_out = (geo_rgb * 255).astype(np.uint8)      # the reference returns this frame when it made one
+            Image.fromarray(img_out).convert("RGB").save(os.path.join(out_render_path, '%04d_geo.png' % img_idx))
+        elif self.vis_geo and not self._warned_geo:
+            logger_py.warning("training.vis_geo: the phong geometry renderer runs only on the GPU; skipping *_geo.png on the CPU")
             self._warned_geo = True
         return img_out

@@ -317,12 +317,13 @@ def render_rays(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor, 
     return _RenderRays.apply(pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts, *weights, *biases)
 
 
-def mlp_points(pts: torch.Tensor, view: torch.Tensor, weights, biases, *, hidden: int):
+def mlp_points(pts: torch.Tensor, view: torch.Tensor, weights, biases, *, hidden: int, split2: bool = False):
     """Forward-only evaluation of the MLP on free-standing points: (S,3),(S,3) -> rgb (S,3), sigma_raw (S,).
-    Each point is rendered as a one-sample ray (origin = point, direction = 0) through the same fused kernel."""
+    Each point is rendered as a one-sample ray (origin = point, direction = 0) through the same fused kernel.
+    split2: the two-term fp16 products whatever lib.set_fp32_products selects (the phong renderer's mode)."""
     _require_gpu(pts)
     S, dev = pts.shape[0], pts.device
-    cfg = L.make_cfg(S, 1, hidden)
+    cfg = split2_cfg(S, 1, hidden) if split2 else L.make_cfg(S, 1, hidden)
     lib = L.load()
     pts = pts.detach().contiguous().float()
     view = view.detach().contiguous().float()
@@ -336,3 +337,63 @@ def mlp_points(pts: torch.Tensor, view: torch.Tensor, weights, biases, *, hidden
     out = workspace_plane(cfg, ws, 0).clone()
     _give_workspace(cfg, dev, ws)
     return out[:, :3], out[:, 3]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the phong geometry renderer (model/rendering.py: Renderer.phong_renderer): the depth search and the surface normals
+# ----------------------------------------------------------------------------------------------------------------------
+def split2_cfg(n_rays: int, n_samples: int, hidden: int, *, dist_alpha=False, relu_sigma=False, train=False) -> L.Cfg:
+    """A cfg in the two-term fp16 mode (NNR_F_SPLIT3 | NNR_F_SPLIT2) regardless of lib.set_fp32_products: the phong renderer always
+    evaluates in this mode (its march kernel exists only in it), so its output does not depend on the training step's product setting."""
+    flags = L.NNR_F_SPLIT3 | L.NNR_F_SPLIT2 | (L.NNR_F_DIST_ALPHA if dist_alpha else 0) | (L.NNR_F_RELU_SIGMA if relu_sigma else 0) | \
+        (L.NNR_F_TRAIN if train else 0)
+    return L.Cfg(int(n_rays), int(n_samples), int(hidden), flags)
+
+
+def ray_march(ray_o: torch.Tensor, ray_d: torch.Tensor, t_table: torch.Tensor, weights, biases, *, hidden: int, radius: float,
+              n_secant: int = 8, relu_sigma: bool = False, dist_alpha: bool = False) -> torch.Tensor:
+    """The reference's ray_marching + secant (model/rendering.py:277-418) in 2 + n_secant launches of nnr_ray_march: (R,3) origins,
+    (R,3) unit directions, the (n_steps) torch.linspace(0, 1, n_steps) table on the device -> d (R): the surface depth on a hit, +inf on a
+    miss, 0 where the first proposal is occupied.  No host synchronisation."""
+    _require_gpu(ray_o)
+    R, dev = ray_o.shape[0], ray_o.device
+    cfg = split2_cfg(R, t_table.shape[0], hidden, dist_alpha=dist_alpha, relu_sigma=relu_sigma)
+    lib = L.load()
+    ray_o = ray_o.detach().contiguous().float()
+    ray_d = ray_d.detach().contiguous().float()
+    t_table = t_table.detach().contiguous().float()
+    packed = _packed_for(cfg, list(weights), list(biases))
+    state = torch.empty(R, 4, dtype=torch.float32, device=dev)
+    d = torch.empty(R, dtype=torch.float32, device=dev)
+    L.check(lib.nnr_ray_march(C.byref(cfg), L.ptr(ray_o), L.ptr(ray_d), float(radius), L.ptr(t_table), int(n_secant), L.ptr(packed),
+                              L.ptr(state), L.ptr(d), L.stream()), "nnr_ray_march")
+    return d
+
+
+_P_DOUT4, _P_DPTS = 2, 3      # workspace planes (nnr_layout.h): the per-sample output gradient, the gradient of the sample's point
+
+
+def density_grad(points: torch.Tensor, weights, biases, hidden: int) -> torch.Tensor:
+    """d(raw density)/d(point) for (S,3) points -> (S,3), first order, with the training kernels and no new MLP code: one training
+    forward with one-sample rays (origin = point, direction = 0, as mlp_points), the output-gradient plane seeded with (0, 0, 0, 1) --
+    d rgb_pre = 0, d sigma_raw = 1, the one plane of the composite backward the input-gradient kernel reads -- then nnr_mlp_dgrad; the
+    answer is its d(point) plane.  Two-term fp16 products (split2_cfg)."""
+    _require_gpu(points)
+    S, dev = points.shape[0], points.device
+    cfg = split2_cfg(S, 1, hidden, train=True)
+    lib = L.load()
+    pts = points.detach().contiguous().float()
+    zeros3 = torch.zeros_like(pts)
+    z0 = torch.zeros(1, dtype=torch.float32, device=dev)
+    packed = _packed_for(cfg, list(weights), list(biases))
+    ws = _take_workspace(cfg, dev)
+    st = L.stream()
+    L.check(lib.nnr_mlp_fwd(C.byref(cfg), L.ptr(pts), L.ptr(zeros3), L.ptr(zeros3), L.ptr(z0), L.ptr(z0), None,
+                            L.ptr(packed), L.ptr(ws), st), "nnr_mlp_fwd")
+    seed = workspace_plane(cfg, ws, _P_DOUT4)
+    seed[:, :3] = 0.
+    seed[:, 3] = 1.
+    L.check(lib.nnr_mlp_dgrad(C.byref(cfg), L.ptr(packed), L.ptr(ws), st), "nnr_mlp_dgrad")
+    g = workspace_plane(cfg, ws, _P_DPTS)[:, :3].clone()
+    _give_workspace(cfg, dev, ws)
+    return g
