@@ -31,7 +31,8 @@ SOURCES = [("nnr_wgrad.hip", ()), ("nnr_wgrad.hip", ("NNR_WGRAD_F16_TU=1",)), ("
 def _obj_name(src, defines):
     tag = "".join("_" + d.split("=")[0].lower().replace("nnr_", "") + d.split("=")[1] for d in defines)
     return os.path.splitext(src)[0] + tag + ".o"
-SPLIT2_ONLY = ["nnr_split2.h"]      # included by the two fp16-term kernels only: touching it does not rebuild the rest (minutes per unit)
+SPLIT2_ONLY = ["nnr_split2.h", "nnr_trunk_f16.h", "nnr_trunk_f16.inc"]      # included by the fp16-term kernels (the `_f16` units) only: touching them does not rebuild the rest (minutes per unit)
+FWD_ONLY = ["nnr_mlp_fwd_common.h"]      # included by nnr_mlp_fwd.hip and, through nnr_trunk_f16.h, by the `_f16` units
 HEADERS = ["nnr_layout.h", "nnr_device.h", "nnr_kernels.h", "nnr_mlp_bf16.h", "nnr_split.h", os.path.join("..", "..", "include", "nnr.h")]
 # -pragma-unroll-threshold: the MLP kernels are straight-line code by construction (every `#pragma unroll` loop must unroll fully, or
 # the register arrays they index fall back to scratch memory).  LLVM caps `#pragma unroll` at 16 K instructions per loop; one GEMM part
@@ -114,7 +115,7 @@ def build(force=False, verbose=False):
     jobs = []
     for src, defines in SOURCES:
         obj = os.path.join(OUT_DIR, _obj_name(src, defines))
-        own = [os.path.join(HERE, h) for h in SPLIT2_ONLY] if "_f16" in src else []
+        own = [os.path.join(HERE, h) for h in (SPLIT2_ONLY + FWD_ONLY if "_f16" in src else FWD_ONLY if src == "nnr_mlp_fwd.hip" else [])]
         if force or _stale(obj, [os.path.join(HERE, src)] + hdrs + own):
             jobs.append([hipcc] + FLAGS + ["-D" + d for d in defines] + ["-c", os.path.join(HERE, src), "-o", obj])
 

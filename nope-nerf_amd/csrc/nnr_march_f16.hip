@@ -1,9 +1,9 @@
 // nnr_march_f16.hip -- the occupancy march of the phong geometry renderer (reference model/rendering.py:277-418): position encoding, the eight
 // trunk layers and the density head of OfficialStaticNerf (official_nerf.py:60-83, only_occupancy=True), nothing of the colour branch, in the
 // two-term fp16 arithmetic of nnr_mlp_fwd_f16.hip (NNR_F_SPLIT3 | NNR_F_SPLIT2, Layout<D, 3>, three fp16 MFMA terms per product, fp32 accumulation,
-// weights through the DMA-fed LDS ring).  The trunk below is that kernel's inference trunk, restated with the training stash, the direction
-// encoding and the colour GEMMs taken out; the weight stream stops in front of the colour panels (n_panels = fwd_panel0(F_RGBH_F)), so a
-// workgroup's passes wrap around the trunk's panels only.
+// weights through the DMA-fed LDS ring).  It shares that kernel's trunk (nnr_trunk_f16.h, TRAIN = false) and has nothing of its direction
+// encoding and colour GEMMs; the weight stream stops in front of the colour panels (n_panels = fwd_panel0(F_RGBH_F)), so a workgroup's
+// passes wrap around the trunk's panels only.
 //
 // Two modes, one kernel:
 //   * ray mode (MarchArgs::flat == 0): one wave walks one ray's n_steps proposals d_j = d_far * t_j in passes of 32 samples (the workgroup four
@@ -17,9 +17,7 @@
 // State encoding: hit = (d_lo, d_hi, f_lo < 0, f_hi); miss = (+inf, +inf, 0, 0); first proposal occupied (val_0 >= 0) = (0, 0, 0, 0).  A hit's
 // f_lo stays negative through every step (it is only ever replaced by an f_mid < 0), so `f_lo < 0` is the hit test; march_finish_kernel turns
 // the state into the reference's d (secant estimate / inf / 0).
-#include "nnr_device.h"
-#include "nnr_kernels.h"
-#include "nnr_split2.h"
+#include "nnr_trunk_f16.h"
 
 namespace nnr {
 
@@ -102,7 +100,6 @@ __global__ __launch_bounds__(256, 1) void march_f16_kernel(MarchArgs a) {
 
     constexpr int HR = 16 * HT;
     constexpr int NP = HR / 2;
-    constexpr int PP = mode_panels(DT, HT, 3);
 
     uint32_t eh[16], em[16];      // gamma_10(p): 63 -> 64 values = 16 pairs
     {
@@ -112,96 +109,21 @@ __global__ __launch_bounds__(256, 1) void march_f16_kernel(MarchArgs a) {
         split2_all(eh, em, [&](int r) { return e[r]; });
     }
     const float* bias = ltab - L::bias_base;
-    auto inv_scale = [&](int slot) __attribute__((always_inline)) {
-        return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(bias[L::scale_off + 16 + slot])));
-    };
 
     uint32_t ph[8 * DT], pm[8 * DT];
     f32x16 accA[HT], accB[HT];
-    float mx = 0.f;                      // running maximum of the activations (the fp16 range check)
+    float mx = 0.f, mxa = 0.f;           // running maximum of the activations (the fp16 range check)
     float sg0 = 0.f, sg1 = 0.f;          // density head: this lane's share of w_sigma . h8
-
-    auto init_acc = [&](f32x16(&acc)[HT], int bias_offset) __attribute__((always_inline)) {
-        const float* b = bias + bias_offset + 4 * half;
-#pragma unroll
-        for (int t = 0; t < HT; ++t)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 bb = *reinterpret_cast<const f32x4*>(b + 32 * t + 8 * q);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[t][4 * q + i] = bb[i];
-            }
-    };
-    // one epilogue unit (nnr_mlp_fwd_f16.hip's NNR_FINISH without the training stash)
-#define NNR_FINISH(ACC, OFFP, INV, SIG)                                                                            \
-    [&](int u) __attribute__((always_inline)) {                                                                  \
-        const int r = 2 * u;                                                                                     \
-        float x0, x1;                                                                                            \
-        unit_fwd_infer(ACC[r >> 4][r & 15], ACC[(r + 1) >> 4][(r + 1) & 15], INV, x0, x1, ph[(OFFP) + u], pm[(OFFP) + u], mx); \
-        if constexpr (SIG) {                                                                                     \
-            const f32x2 w2 = *reinterpret_cast<const f32x2*>(bias + L::wsig_off + half * (16 * DT) + 2 * (OFFP) + r); \
-            sg0 = fmaf(w2[0], x0, sg0);                                                                          \
-            sg1 = fmaf(w2[1], x1, sg1);                                                                          \
-        }                                                                                                        \
+    {   // the trunk, nothing of the training side
+        constexpr bool TRAIN = false;
+        const TrunkStash st{};
+        auto xh = [](int) -> const char* { return nullptr; };
+        auto p0 = [&](int part) { return L::fwd_panel0(part); };
+#include "nnr_trunk_f16.inc"
     }
-    auto p0 = [&](int part) { return L::fwd_panel0(part); };
-
-    // hidden 1: 63 -> D, input = posenc
-    init_acc(accA, L::bias_off(0));
-    gemm_part2<2, HT>(accA, eh, em, pipe, p0(F_L1A));
-    init_acc(accB, L::bias_off(0) + L::Dh);
-    {
-        const float inv = inv_scale(0);
-        gemm_part2<2, HT, NP, 0, NP / 4, 0, 0>(accB, eh, em, pipe, p0(F_L1B), NNR_FINISH(accA, 0, inv, false));
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        park[q * 64] = __builtin_bit_cast(f32x4, u32x4{eh[4 * q], eh[4 * q + 1], eh[4 * q + 2], eh[4 * q + 3]});
-        park[(4 + q) * 64] = __builtin_bit_cast(f32x4, u32x4{em[4 * q], em[4 * q + 1], em[4 * q + 2], em[4 * q + 3]});
-    }
-    auto dense_layer = [&](int li, int pa, auto sig_tag) __attribute__((always_inline)) {
-        constexpr bool SIG = decltype(sig_tag)::value;
-        init_acc(accA, L::bias_off(li));
-        {
-            const float inv = inv_scale(li - 1);
-            gemm_part2<DT, HT, NP, 1, 0, 0, 0>(accA, ph, pm, pipe, pa, NNR_FINISH(accB, NP, inv, false));
-        }
-        init_acc(accB, L::bias_off(li) + L::Dh);
-        {
-            const float inv = inv_scale(li);
-            gemm_part2<DT, HT, NP, 2, 0, 0, 0>(accB, ph, pm, pipe, pa + PP, NNR_FINISH(accA, 0, inv, SIG));
-        }
-    };
-    // hidden 2..4
-#pragma unroll 1
-    for (int l = 0; l < 3; ++l) dense_layer(1 + l, p0(F_L2A) + 2 * PP * l, std::false_type{});
-    // hidden 5: [h4 ; e] -> D (the skip connection, official_nerf.py:63)
-    init_acc(accA, L::bias_off(4));
-    {
-        const float inv = inv_scale(3);
-        gemm_part2<DT, HT, NP, 1, 0, 0, 0>(accA, ph, pm, pipe, p0(F_L5HA), NNR_FINISH(accB, NP, inv, false));
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const u32x4 vh = __builtin_bit_cast(u32x4, park[q * 64]), vm = __builtin_bit_cast(u32x4, park[(4 + q) * 64]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { eh[4 * q + i] = vh[i]; em[4 * q + i] = vm[i]; }
-    }
-    gemm_part2<2, HT>(accA, eh, em, pipe, p0(F_L5EA));
-    init_acc(accB, L::bias_off(4) + L::Dh);
-    {
-        const float inv = inv_scale(4);
-        gemm_part2<DT, HT, NP, 2, 0, 0, 0>(accB, ph, pm, pipe, p0(F_L5HB), NNR_FINISH(accA, 0, inv, false));
-    }
-    gemm_part2<2, HT>(accB, eh, em, pipe, p0(F_L5EB));
-    // hidden 6, 7, 8
-#pragma unroll 1
-    for (int l = 0; l < 2; ++l) dense_layer(5 + l, p0(F_L6A) + 2 * PP * l, std::false_type{});
-    dense_layer(7, p0(F_L6A) + 2 * PP * 2, std::true_type{});
-#undef NNR_FINISH
     {   // hidden 8, half B: no colour GEMM to hide it under -- finished here in plain code (the units' inline asm reads accumulators with no
         // hazard cover of its own; here the compiler sees the MFMA results it reads), the same products as unit_fwd_infer and the head's other half
-        const float inv = inv_scale(7);
+        const float inv = inv_scale<L>(bias, 7);
 #pragma unroll
         for (int u = 0; u < NP; ++u) {
             const int r = 2 * u;
@@ -214,8 +136,7 @@ __global__ __launch_bounds__(256, 1) void march_f16_kernel(MarchArgs a) {
     }
     const float sg = sg0 + sg1;
     float raw = sg + __shfl_xor(sg, 32, 64) + bias[L::bias_off(8)];
-    // the two-term arithmetic's one bound (include/nnr.h, NNR_F_SPLIT2): an activation that left fp16's range makes the sample NaN
-    if (!(fmaxf(mx, __shfl_xor(mx, 32, 64)) < 65520.f)) raw = __uint_as_float(0x7fc00000u);
+    if (left_f16_range(mx)) raw = __uint_as_float(0x7fc00000u);
     const float val = march_val(raw, a.flags);
 
     if (a.flat) {      // one secant step (:404-417) on the rays that are hits

@@ -11,8 +11,7 @@
 // (fp32 products; the bf16-MFMA mode has its own kernel, nnr_mlp_fwd_bf16.hip)
 // MODE 2 (NNR_F_SPLIT3): the same kernel with every GEMM part's products taken as six bf16 MFMA terms -- only the weight stream (24 KiB
 // panels of pre-split fragments) and gemm_part (nnr_split.h) differ; 2.7 times fewer matrix-pipe cycles, fp32-equivalent results.
-#include "nnr_device.h"
-#include "nnr_kernels.h"
+#include "nnr_mlp_fwd_common.h"
 #include "nnr_split.h"
 
 namespace nnr {
@@ -111,22 +110,6 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(MlpFwdArgs a) {
     f32x16 accA[HT], accB[HT];   // halves A ([0,D/2)) and B ([D/2,D)) of the layer being computed
     uint32_t mwA[HW], mwB[HW];
 
-    // accumulators start at the bias, so an epilogue is only ReLU (+ sign bit) or a move
-    auto init_acc = [&](f32x16(&acc)[HT], int bias_offset) __attribute__((always_inline)) {
-        const float* b = bias + bias_offset + 4 * half;
-#pragma unroll
-        for (int t = 0; t < HT; ++t)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 bb = *reinterpret_cast<const f32x4*>(b + 32 * t + 8 * q);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[t][4 * q + i] = bb[i];
-            }
-    };
-    auto clear_mask = [&](uint32_t(&mw)[HW]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int w = 0; w < HW; ++w) mw[w] = 0;
-    };
     constexpr bool kGateSplit = MODE == 2 && TRAIN && !kAblateNoMask;     // see NNR_RELU_PAIR below
     auto store_gates = [&](int layer_idx) __attribute__((always_inline)) {      // both halves of a hidden layer's gates, from the pipe
         if constexpr (kGateSplit) {
@@ -137,9 +120,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(MlpFwdArgs a) {
     };
     auto store_mask = [&](const uint32_t(&mw)[HW], int layer_idx, int hb) __attribute__((always_inline)) {
         if (TRAIN && !(kGateSplit && layer_idx < 8)) {
-            uint32_t* m = mask_base + (int64_t)layer_idx * 64 * L::mask_words + hb * HW;
-#pragma unroll
-            for (int w = 0; w < HW; ++w) m[w] = mw[w];
+            nnr::store_mask<L>(mask_base, mw, layer_idx, hb);
         }
     };
 // one epilogue unit u (registers 2u, 2u+1 of the half): h[off + 2u + i] = relu(acc) (+ sign bit) or plain move.  Mask bit r = (x > 0).
@@ -172,9 +153,9 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(MlpFwdArgs a) {
     };
 
     // ---- hidden 1: 63 -> D, input = posenc.  Pass A, then pass B with A's epilogue hidden under it. ----
-    init_acc(accA, L::bias_off(0));
+    init_acc(accA, bias, L::bias_off(0), half);
     gemm_part<2, HT, TRAIN>(accA, e, pipe, p0(F_L1A), xe);
-    init_acc(accB, L::bias_off(0) + L::Dh);
+    init_acc(accB, bias, L::bias_off(0) + L::Dh, half);
     clear_mask(mwA);
     gemm_part<2, HT, false, NP, NP / 8, 0>(accB, e, pipe, p0(F_L1B), nullptr, NNR_RELU_PAIR(accA, 0, mwA));
     store_mask(mwA, 0, 0);
@@ -186,7 +167,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(MlpFwdArgs a) {
 
     // one D -> D ReLU layer (state_dict index `li`, previous layer index li-1), packed at panel pa
     auto dense_layer = [&](int li, int pa, float* stash) __attribute__((always_inline)) {
-        init_acc(accA, L::bias_off(li));
+        init_acc(accA, bias, L::bias_off(li), half);
         clear_mask(mwB);
         // pass A: the first half of the k-groups only needs h[0,HR); the previous layer's half B is finished meanwhile
         pipe.gates_on = kGateSplit;
@@ -194,7 +175,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(MlpFwdArgs a) {
         pipe.gates_on = false;
         store_gates(li - 1);
         store_mask(mwB, li - 1, 1);
-        init_acc(accB, L::bias_off(li) + L::Dh);
+        init_acc(accB, bias, L::bias_off(li) + L::Dh, half);
         clear_mask(mwA);
         // pass B: half A of the new layer replaces h[0,HR) in place, one k-group behind the reads
         pipe.part_pre = TRAIN && MODE == 2 && PP >= 2 ? 6 : 0;   // pass A's last rows stashed (nnr_split.h)
@@ -207,7 +188,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(MlpFwdArgs a) {
     for (int l = 0; l < 3; ++l) dense_layer(1 + l, p0(F_L2A) + 2 * PP * l, xh(l));
     NNR_STAMP(tl_fwd, (TRAIN ? 0 : 16) + 4);
     // hidden 5: [h4 ; e] -> D   (skip connection, input order [h, posenc]: model/official_nerf.py:63)
-    init_acc(accA, L::bias_off(4));
+    init_acc(accA, bias, L::bias_off(4), half);
     clear_mask(mwB);
     pipe.gates_on = kGateSplit;
     gemm_part<DT, HT, TRAIN, NP, 2, 0>(accA, h, pipe, p0(F_L5HA), xh(3), NNR_RELU_PAIR(accB, HR, mwB));
@@ -222,7 +203,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(MlpFwdArgs a) {
         for (int i = 0; i < 4; ++i) e5[4 * q + i] = v[i];
     }
     gemm_part<2, HT>(accA, e5, pipe, p0(F_L5EA));
-    init_acc(accB, L::bias_off(4) + L::Dh);
+    init_acc(accB, bias, L::bias_off(4) + L::Dh, half);
     clear_mask(mwA);
     gemm_part<DT, HT, false, NP, 2, 1>(accB, h, pipe, p0(F_L5HB), nullptr, NNR_RELU_PAIR(accA, 0, mwA));
     gemm_part<2, HT>(accB, e5, pipe, p0(F_L5EB));
@@ -238,7 +219,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_kernel(MlpFwdArgs a) {
     // Its side work first finishes hidden 8 (half B), then evaluates the density head -- a per-lane dot product of h8 with
     // the density row (a 1-row GEMM is not MFMA work).
     float* const xf = !TRAIN ? nullptr : kTileX ? a.ws_xf + chunk_id * (int64_t)((kDirPad / 8) * 256) + 4 * lane : a.ws_xf + ss * kDirPad + 4 * half;
-    init_acc(accA, L::bias_off(10));
+    init_acc(accA, bias, L::bias_off(10), half);
     clear_mask(mwB);
     float sg0 = 0.f, sg1 = 0.f;
     {
@@ -368,8 +349,7 @@ extern "C" int nnr_timeline_fwd(unsigned long long* host32) {
 #endif
 template <>
 hipError_t launch_mlp_fwd_variant<NNR_FWD_D, (NNR_FWD_TRAIN != 0), NNR_FWD_MODE>(const MlpFwdArgs& a, hipStream_t st) {
-    // ray mode: one workgroup per 4 rays, chunks_per_ray passes each; flat mode: one workgroup per 128 samples
-    dim3 grid((unsigned)(a.chunks_per_ray > 0 ? a.S_pad / kBlockSamples / a.chunks_per_ray : a.S_pad / kBlockSamples)), block(256);
+    dim3 grid = mlp_fwd_grid(a), block(256);
     constexpr bool train = NNR_FWD_TRAIN != 0;
     prof_before(train ? PROF_FWD_TRAIN : PROF_FWD_INFER, st);
     hipLaunchKernelGGL((mlp_fwd_kernel<NNR_FWD_D, train, NNR_FWD_MODE>), grid, block, 0, st, a);

@@ -23,7 +23,8 @@ NNR_F_SPLIT2 = 64
 # How the fp32 mode multiplies in the forward and input-gradient kernels (include/nnr.h, NNR_F_SPLIT3 / NNR_F_SPLIT2):
 #   "split2" (round 6, the default) = every operand as TWO fp16 terms (power-of-two scaled, the residual carried at 2^11), three fp16 MFMAs per
 #            product with fp32 accumulation (csrc/nnr_split2.h) -- half the matrix-pipe passes of "split3", as close to an fp64 evaluation of the
-#            step (tests/test_gpu_split2.py); the weight gradient keeps split3's six bf16 terms;
+#            step (tests/test_gpu_parity.py, tests/test_gpu_layer_local.py); the weight gradient takes three fp16 terms per product too, its
+#            operands scaled by the stashed planes' maxima (csrc/nnr_wgrad.hip);
 #   "split3" = every operand as three bf16 terms, six bf16 MFMAs per product (tests/test_gpu_split3.py): no range bound at all;
 #   "mfma"   = v_mfma_f32_32x32x2_f32.
 PRODUCT_KINDS = ("split2", "split3", "mfma")
