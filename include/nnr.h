@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define NNR_ABI_VERSION 7
+#define NNR_ABI_VERSION 8
 
 /* error codes */
 #define NNR_OK 0
@@ -162,6 +162,21 @@ int nnr_ws_plane_layout(const nnr_cfg* cfg, int plane);
  * 2 + n_secant launches on `stream`, no host synchronisation.  (ABI 7) */
 int nnr_ray_march(const nnr_cfg* cfg, const float* ray_o, const float* ray_d, float radius, const float* t_table, int32_t n_secant,
                   const float* packed, float* state, float* d_out, void* stream);
+
+/* Hierarchical sampling (rendering.num_fine; no reference counterpart -- NeRF's sample_pdf with stratified u): from the alphas and depths of a
+ * coarse render, n_fine more depths per ray drawn from the piecewise-constant density the compositor's weights define, merged with the coarse
+ * depths into one sorted row.  alpha, z: (R,C) as nnr_render_fwd's opt_alpha / opt_z; xi: (R,F) in [0,1) or NULL (= 0.5 everywhere).  Per ray:
+ *   T_i = prod_{j<i} (1 - a_j + 1e-6), w_i = a_i T_i (the compositor's weights); edges m_i = (z_i + z_{i+1}) / 2, i = 0..C-2; bins k = 0..C-3
+ *   of mass p_k = w_{k+1} + 1e-5, normalised by their sum; cdf_0 = 0, cdf_{k+1} = cdf_k + p_k; u_j = (j + xi_j) / F;
+ *   i = #{k : cdf_k <= u_j}, below = max(i-1, 0), above = min(i, C-2), den = cdf[above] - cdf[below] (1 where below 1e-5),
+ *   s_j = m[below] + (u_j - cdf[below]) / den * (m[above] - m[below]), clamped to [m[below], m[above]] (a no-op in exact arithmetic; it keeps the
+ *   rounded samples in order, and an xi that is NaN gives s_j = m[below]).
+ * z_all (R, C+F): the merge of the coarse depths and the s_j, non-decreasing, coarse before fine on ties (an element's position = its own index
+ * + its rank in the other list); fine (R,F) or NULL: the s_j on their own.  A ray with a NaN in alpha or z gets an all-NaN row (both outputs).
+ * One wave per ray, fixed-order scans: bit-reproducible.  3 <= C, 1 <= F, C + F <= 1024; NNR_E_BADCFG for sizes outside that or a null
+ * pointer, NNR_E_UNSUPPORTED for C + F > 1024, NNR_E_ALIGN for a pointer that is not 16-byte aligned.  One launch, no host synchronisation.  (ABI 8) */
+int nnr_resample(int32_t n_rays, int32_t n_coarse, int32_t n_fine, const float* alpha, const float* z, const float* xi, float* z_all,
+                 float* fine, void* stream);
 
 /* Individual stages, exported for profiling and bench.py's per-kernel roofline timing.  Same arguments
  * and workspace contract as the fused entry points above. */

@@ -753,6 +753,17 @@ int nnr_ray_march(const nnr_cfg* cfg, const float* ray_o, const float* ray_d, fl
     return e == hipSuccess ? NNR_OK : hip_fail(e);
 }
 
+// hierarchical sampling: coarse alphas and depths -> the sorted union of the coarse depths and n_fine inverse-CDF samples (nnr_resample.hip)
+int nnr_resample(int32_t n_rays, int32_t n_coarse, int32_t n_fine, const float* alpha, const float* z, const float* xi, float* z_all,
+                 float* fine, void* stream) {
+    if (n_rays <= 0 || n_coarse < 3 || n_fine < 1) return NNR_E_BADCFG;
+    if ((int64_t)n_coarse + n_fine > 1024) return NNR_E_UNSUPPORTED;
+    if (!alpha || !z || !z_all) return NNR_E_BADCFG;      // (xi and fine may be null)
+    if (!aligned16(alpha) || !aligned16(z) || !aligned16(xi) || !aligned16(z_all) || !aligned16(fine)) return NNR_E_ALIGN;
+    hipError_t e = launch_resample(n_rays, n_coarse, n_fine, alpha, z, xi, z_all, fine, (hipStream_t)stream);
+    return e == hipSuccess ? NNR_OK : hip_fail(e);
+}
+
 int nnr_composite_bwd(const nnr_cfg* cfg, const float* d_rgb, const float* d_dist, float* ws, void* stream) {
     int rc = check_cfg(cfg);
     if (rc != NNR_OK) return rc;

@@ -243,6 +243,8 @@ hipError_t launch_mlp_fwd_bf16(int D, const MlpFwdArgs& a, bool train, hipStream
 hipError_t launch_mlp_dgrad_bf16(int D, const MlpDgradArgs& a, hipStream_t st);              // nnr_mlp_dgrad_bf16.hip
 hipError_t launch_march(int D, const MarchArgs& a, hipStream_t st);                              // nnr_march_f16.hip
 hipError_t launch_march_finish(const float* state, float* d_out, int R, hipStream_t st);
+// hierarchical sampling (nnr_resample.hip): alpha, z (R,C), xi (R,F) or null -> z_all (R,C+F), fine (R,F) or null
+hipError_t launch_resample(int R, int C, int F, const float* alpha, const float* z, const float* xi, float* z_all, float* fine, hipStream_t st);
 hipError_t launch_composite_fwd(const CompositeArgs& a, hipStream_t st);
 hipError_t launch_composite_bwd(const CompositeArgs& a, hipStream_t st);
 hipError_t launch_ray_reduce(const RayReduceArgs& a, hipStream_t st);

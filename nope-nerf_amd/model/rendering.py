@@ -7,6 +7,10 @@ distortion exactly as they do through the reference's matrix inverses), and ONE 
 `nnr.render_rays` for everything per-sample: stratified / NDC sampling, positional encoding, the 12-layer MLP,
 alpha-compositing, and their backward.
 
+`rendering.num_fine: F` (default 0 = off; the reference has no counterpart) turns the render into NeRF's hierarchical sampling with one
+network: a coarse forward-only pass at the `num_points - outside_steps` samples above, `nnr.ops.resample` (nnr_resample.hip) for F more
+depths per ray from the coarse weights' inverse CDF, and the render proper -- the training path -- at the sorted union of both sets.
+
 `rendering.normal_loss: True` (reference :133-143; off by default, and no loss term of the reference consumes it) adds the
 normal-consistency vector `out['normal']`: second-order autograd through the MLP trunk for the 2 M surface points, in stock torch
 over the same nn.Linear parameters (OfficialStaticNerf.gradient) -- the fused kernels still render.
@@ -108,6 +112,25 @@ class Renderer(nn.Module):
             self._z_cache[key] = hit
         return hit
 
+    def _unit_tables(self, n, device):
+        """z_lo = 0, z_hi = 1 of n samples: with them the render kernels' z = z_lo + (z_hi - z_lo) * jitter is the jitter tensor bit for
+        bit -- how the fine pass of hierarchical sampling hands over per-ray depths.  Cached per size."""
+        key = ('unit', int(n), str(device))
+        hit = self._z_cache.get(key)
+        if hit is None:
+            hit = (torch.zeros(n, device=device), torch.ones(n, device=device))
+            self._z_cache[key] = hit
+        return hit
+
+    def _fine_draw(self, n_rays, n_fine, device):
+        """xi (R, num_fine) in [0,1): the stratified offsets of the fine samples, drawn right after the jitter.  A data-parallel shard takes
+        its rows of the whole step's draw, as for the jitter, so that every rank's generator ends where the single-process run's does."""
+        if self.jitter_window is None:
+            return torch.rand(n_rays, n_fine, device=device)
+        lo, total = self.jitter_window
+        from nnr import sampling
+        return sampling.rand_rows(total * n_fine, lo * n_fine, n_rays * n_fine, device).view(n_rays, n_fine)
+
     # ------------------------------------------------------------------------------------------------ hot path
     def nope_nerf(self, pixels, depth, camera_mat, world_mat, scale_mat, add_noise=False, it=100000, eval_=False, rays=None):
         cfg = self.cfg
@@ -171,6 +194,19 @@ class Renderer(nn.Module):
         kw = dict(hidden=net.hidden_dim, dist_alpha=bool(cfg['dist_alpha']), white_bg=bool(self.white_background),
                   relu_sigma=(net.occ_activation != 'softplus'),
                   bf16=(str(cfg.get('mfma_dtype', 'fp32')).lower() == 'bf16'))   # rendering.mfma_dtype: fp32 (default) | bf16
+        n_fine = int(cfg.get('num_fine', 0) or 0)    # rendering.num_fine: hierarchical sampling, 0 / absent = off (nothing below changes)
+        if n_fine > 0:
+            if not pixels.is_cuda:
+                raise NotImplementedError("rendering.num_fine > 0 runs only on the GPU (HIP resampling kernel, nnr_resample.hip); there is no "
+                                          "CPU hierarchical sampling -- set rendering.num_fine: 0 for CPU runs")
+            # coarse pass (the inference forward: no stash, only alpha and z) -> nnr_resample -> the render proper at the sorted union of
+            # the coarse depths and n_fine inverse-CDF samples of the coarse weights.  One network, trained at both sample sets; the
+            # depths carry no gradient, pose / distortion gradients flow through pts_o / pts_d as before.
+            xi = self._fine_draw(n_rays, n_fine, device) if (jitter is not None) else None   # after the jitter draw; else u at bin centres
+            with torch.no_grad():
+                _, _, alpha_c, z_c = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(), samples=True, **kw)
+            z_lo, z_hi = self._unit_tables(n_samples + n_fine, device)      # z = 0 + (1 - 0) * jitter: the kernels take the depths as given
+            jitter = _nnr_ops.resample(alpha_c, z_c, xi, n_fine)
         lazy_samples = not torch.is_grad_enabled()   # evaluation / visualisation: per-sample outputs only if somebody reads them
         rgb, dist_pred, alpha, z_val = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(),
                                                        samples=not lazy_samples, **kw)

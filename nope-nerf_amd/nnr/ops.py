@@ -397,3 +397,24 @@ def density_grad(points: torch.Tensor, weights, biases, hidden: int) -> torch.Te
     g = workspace_plane(cfg, ws, _P_DPTS)[:, :3].clone()
     _give_workspace(cfg, dev, ws)
     return g
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# hierarchical sampling (model/rendering.py: rendering.num_fine)
+# ----------------------------------------------------------------------------------------------------------------------
+def resample(alpha: torch.Tensor, z: torch.Tensor, xi: Optional[torch.Tensor], n_fine: int, return_fine: bool = False):
+    """alpha, z (R,C) of a coarse render (render_rays' per-sample outputs), xi (R,n_fine) in [0,1) or None (= 0.5) -> z_all (R, C + n_fine):
+    per ray the coarse depths and n_fine inverse-CDF samples of the compositor's weights, merged and sorted (nnr_resample, include/nnr.h).
+    return_fine: also the (R,n_fine) fine samples on their own.  Not differentiable (the depths carry no gradient).  One launch, no host
+    synchronisation."""
+    _require_gpu(alpha)
+    R, Cn = alpha.shape
+    F = int(n_fine)
+    dev = alpha.device
+    alpha = alpha.detach().contiguous().float()
+    z = z.detach().contiguous().float().view(R, Cn)
+    xi = xi.detach().contiguous().float().view(R, F) if xi is not None else None
+    z_all = torch.empty(R, Cn + max(F, 0), dtype=torch.float32, device=dev)
+    fine = torch.empty(R, max(F, 0), dtype=torch.float32, device=dev) if return_fine else None
+    L.check(L.load().nnr_resample(R, Cn, F, L.ptr(alpha), L.ptr(z), L.ptr(xi), L.ptr(z_all), L.ptr(fine), L.stream()), "nnr_resample")
+    return (z_all, fine) if return_fine else z_all
