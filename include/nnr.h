@@ -178,6 +178,25 @@ int nnr_ray_march(const nnr_cfg* cfg, const float* ray_o, const float* ray_d, fl
 int nnr_resample(int32_t n_rays, int32_t n_coarse, int32_t n_fine, const float* alpha, const float* z, const float* xi, float* z_all,
                  float* fine, void* stream);
 
+/* The proposal stage of hierarchical sampling in ONE launch (rendering.proposal: 'density'): the density of the C coarse samples of every ray
+ * and nnr_resample's row code on it, nothing per sample through HBM (nnr_propose_f16.hip).  cfg: n_rays = R, n_samples = C, hidden 128 / 256,
+ * flags NNR_F_SPLIT3 | NNR_F_SPLIT2 (required, as for nnr_ray_march: the kernel evaluates in the two-term fp16 arithmetic, `packed` is that
+ * mode's buffer) plus NNR_F_DIST_ALPHA / NNR_F_RELU_SIGMA; NNR_F_TRAIN or NNR_F_BF16 -> NNR_E_UNSUPPORTED (NNR_F_WHITE_BG is ignored: no colour).
+ * pts_o, pts_d (R,3), z_lo, z_hi (C), jitter (R,C) or NULL: nnr_render_fwd's sampling, z_j = z_lo_j + (z_hi_j - z_lo_j) jitter_j (z_lo_j
+ * without jitter) and p_j = o + d z_j rounded as there; no view direction -- the density does not depend on it.  alpha_j: the compositor's
+ * (nnr_render_fwd's opt_alpha) from the trunk and the density head alone; a sample whose activations leave fp16's range (NNR_F_SPLIT2), whose
+ * point is not finite or whose raw density is NaN has alpha = NaN.  xi (R,F) or NULL, z_all (R, C+F): as nnr_resample's, fed with these alphas and
+ * depths: a ray with a NaN alpha or z gets an all-NaN row.  opt_alpha (R,C), opt_z (R,C), opt_fine (R,F): the kernel's alphas, depths and fine
+ * samples, written where non-NULL (tests and tools; the renderer passes NULL).
+ * 3 <= C <= 256, 1 <= F, C + F <= 1024 (the alphas and depths of a ray wait in LDS beside the weight ring and the tables while the passes
+ * run: 8 KB per workgroup at C = 256; the rows of the resampling stage take the ring's place after the last pass); NNR_E_BADCFG for smaller
+ * sizes or a null required pointer, NNR_E_UNSUPPORTED for C > 256, C + F > 1024, another hidden width or the flags above, NNR_E_ALIGN for
+ * `packed` or z_all not 16-byte aligned (the kernel's 16-byte accesses) or any other pointer not 4-byte aligned.  One launch, no host
+ * synchronisation, no atomics: bit-reproducible.  (Added under ABI 8: a new function changes no existing signature or layout.) */
+int nnr_propose(const nnr_cfg* cfg, int32_t n_fine, const float* pts_o, const float* pts_d, const float* z_lo, const float* z_hi,
+                const float* jitter, const float* xi, const float* packed, float* z_all, float* opt_alpha, float* opt_z, float* opt_fine,
+                void* stream);
+
 /* Individual stages, exported for profiling and bench.py's per-kernel roofline timing.  Same arguments
  * and workspace contract as the fused entry points above. */
 int nnr_mlp_fwd(const nnr_cfg* cfg, const float* pts_o, const float* pts_d, const float* view_d,

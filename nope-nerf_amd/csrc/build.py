@@ -15,7 +15,7 @@ LIB = os.path.join(os.path.dirname(HERE), "nnr", "libnnr.so")
 SOURCES = [("nnr_wgrad.hip", ()), ("nnr_wgrad.hip", ("NNR_WGRAD_F16_TU=1",)), ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=256",)),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=0")),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=128",)),
-           ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_march_f16.hip", ()),
+           ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_march_f16.hip", ()), ("nnr_propose_f16.hip", ()),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MODE=2")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_MODE=2")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=0", "NNR_FWD_MODE=2")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1", "NNR_FWD_MODE=2")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=128", "NNR_DGRAD_MODE=2")),
@@ -32,6 +32,7 @@ def _obj_name(src, defines):
     tag = "".join("_" + d.split("=")[0].lower().replace("nnr_", "") + d.split("=")[1] for d in defines)
     return os.path.splitext(src)[0] + tag + ".o"
 SPLIT2_ONLY = ["nnr_split2.h", "nnr_trunk_f16.h", "nnr_trunk_f16.inc"]      # included by the fp16-term kernels (the `_f16` units) only: touching them does not rebuild the rest (minutes per unit)
+ROW_ONLY = ["nnr_resample_row.h"]      # the row code of hierarchical sampling: nnr_resample.hip and nnr_propose_f16.hip
 FWD_ONLY = ["nnr_mlp_fwd_common.h"]      # included by nnr_mlp_fwd.hip and, through nnr_trunk_f16.h, by the `_f16` units
 HEADERS = ["nnr_layout.h", "nnr_device.h", "nnr_kernels.h", "nnr_mlp_bf16.h", "nnr_split.h", os.path.join("..", "..", "include", "nnr.h")]
 # -pragma-unroll-threshold: the MLP kernels are straight-line code by construction (every `#pragma unroll` loop must unroll fully, or
@@ -49,7 +50,7 @@ SCRATCH_LIMIT = {"18mlp_fwd_f16_kernelI": 0, "18mlp_fwd_f16_kernelILi256ELb0E": 
                  "20mlp_dgrad_f16_kernelI": 0, "14mlp_fwd_kernelI": 0, "14mlp_fwd_kernelILi256ELb1ELi2E": 48, "16mlp_dgrad_kernelI": 0, "12wgrad_kernelI": 0, "14wgrad_b_kernelE": 0,
                  "19mlp_fwd_bf16_kernelI": 48, "19mlp_fwd_bf16_kernelILi256ELb1E": 16, "19mlp_fwd_bf16_kernelILi128ELb1E": 16,
                  "21mlp_dgrad_bf16_kernelI": 64, "20composite_fwd_kernelE": 0, "20composite_bwd_kernelE": 0,
-                 "16march_f16_kernelI": 0, "19march_finish_kernel": 0, "15resample_kernelE": 0}
+                 "16march_f16_kernelI": 0, "19march_finish_kernel": 0, "15resample_kernelE": 0, "18propose_f16_kernelI": 0}
 
 
 def check_resources(remarks, what):
@@ -116,6 +117,7 @@ def build(force=False, verbose=False):
     for src, defines in SOURCES:
         obj = os.path.join(OUT_DIR, _obj_name(src, defines))
         own = [os.path.join(HERE, h) for h in (SPLIT2_ONLY + FWD_ONLY if "_f16" in src else FWD_ONLY if src == "nnr_mlp_fwd.hip" else [])]
+        own += [os.path.join(HERE, h) for h in (ROW_ONLY if src in ("nnr_resample.hip", "nnr_propose_f16.hip") else [])]
         if force or _stale(obj, [os.path.join(HERE, src)] + hdrs + own):
             jobs.append([hipcc] + FLAGS + ["-D" + d for d in defines] + ["-c", os.path.join(HERE, src), "-o", obj])
 

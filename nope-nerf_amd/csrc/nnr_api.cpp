@@ -764,6 +764,28 @@ int nnr_resample(int32_t n_rays, int32_t n_coarse, int32_t n_fine, const float* 
     return e == hipSuccess ? NNR_OK : hip_fail(e);
 }
 
+// the proposal stage of hierarchical sampling in one launch: coarse densities + the resampling row code (nnr_propose_f16.hip)
+int nnr_propose(const nnr_cfg* cfg, int32_t n_fine, const float* pts_o, const float* pts_d, const float* z_lo, const float* z_hi,
+                const float* jitter, const float* xi, const float* packed, float* z_all, float* opt_alpha, float* opt_z, float* opt_fine,
+                void* stream) {
+    if (!cfg || cfg->n_rays <= 0 || cfg->n_samples < 3 || n_fine < 1) return NNR_E_BADCFG;
+    if (cfg->hidden != 128 && cfg->hidden != 256) return NNR_E_UNSUPPORTED;
+    if (cfg->n_samples > kProposeMaxC || (int64_t)cfg->n_samples + n_fine > 1024) return NNR_E_UNSUPPORTED;
+    if ((cfg->flags & (NNR_F_TRAIN | NNR_F_BF16)) || !is_split2(cfg)) return NNR_E_UNSUPPORTED;
+    if (!pts_o || !pts_d || !z_lo || !z_hi || !packed || !z_all) return NNR_E_BADCFG;      // (jitter, xi and the opt_* may be null)
+    if (!aligned16(packed) || !aligned16(z_all)) return NNR_E_ALIGN;
+    for (const void* p : {(const void*)pts_o, (const void*)pts_d, (const void*)z_lo, (const void*)z_hi, (const void*)jitter, (const void*)xi,
+                          (const void*)opt_alpha, (const void*)opt_z, (const void*)opt_fine})
+        if (reinterpret_cast<uintptr_t>(p) & 3u) return NNR_E_ALIGN;
+    ProposeArgs a{};
+    a.pts_o = pts_o; a.pts_d = pts_d; a.z_lo = z_lo; a.z_hi = z_hi; a.jitter = jitter; a.xi = xi; a.packed = packed;
+    a.z_all = z_all; a.opt_alpha = opt_alpha; a.opt_z = opt_z; a.opt_fine = opt_fine;
+    a.R = cfg->n_rays; a.C = cfg->n_samples; a.F = n_fine;
+    a.flags = cfg->flags & (NNR_F_RELU_SIGMA | NNR_F_DIST_ALPHA);
+    hipError_t e = launch_propose(cfg->hidden, a, (hipStream_t)stream);
+    return e == hipSuccess ? NNR_OK : hip_fail(e);
+}
+
 int nnr_composite_bwd(const nnr_cfg* cfg, const float* d_rgb, const float* d_dist, float* ws, void* stream) {
     int rc = check_cfg(cfg);
     if (rc != NNR_OK) return rc;

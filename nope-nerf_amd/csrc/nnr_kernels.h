@@ -48,6 +48,20 @@ struct MarchArgs {
     int flat;
 };
 
+// the fused proposal stage of hierarchical sampling (nnr_propose_f16.hip): the coarse samples' density and nnr_resample's row code in one launch
+struct ProposeArgs {
+    const float *pts_o, *pts_d;   // (R,3)
+    const float *z_lo, *z_hi;     // (C)
+    const float* jitter;          // (R,C) or null
+    const float* xi;              // (R,F) or null
+    const float* packed;          // Layout<D, 3> (NNR_F_SPLIT3 | NNR_F_SPLIT2)
+    float* z_all;                 // (R,C+F)
+    float *opt_alpha, *opt_z, *opt_fine;   // (R,C), (R,C), (R,F) or null
+    int R, C, F;
+    uint32_t flags;               // NNR_F_RELU_SIGMA / NNR_F_DIST_ALPHA
+};
+constexpr int kProposeMaxC = 256;      // coarse samples per ray the kernel's LDS staging holds (include/nnr.h: nnr_propose)
+
 struct MlpDgradArgs {
     const float* packed;
     float* ws_dout4;        // (S_pad,4): d rgb_pre[3], d sigma_raw (rows >= S are zero-filled here)
@@ -245,6 +259,7 @@ hipError_t launch_march(int D, const MarchArgs& a, hipStream_t st);             
 hipError_t launch_march_finish(const float* state, float* d_out, int R, hipStream_t st);
 // hierarchical sampling (nnr_resample.hip): alpha, z (R,C), xi (R,F) or null -> z_all (R,C+F), fine (R,F) or null
 hipError_t launch_resample(int R, int C, int F, const float* alpha, const float* z, const float* xi, float* z_all, float* fine, hipStream_t st);
+hipError_t launch_propose(int D, const ProposeArgs& a, hipStream_t st);                          // nnr_propose_f16.hip
 hipError_t launch_composite_fwd(const CompositeArgs& a, hipStream_t st);
 hipError_t launch_composite_bwd(const CompositeArgs& a, hipStream_t st);
 hipError_t launch_ray_reduce(const RayReduceArgs& a, hipStream_t st);

@@ -27,29 +27,10 @@
 // region.  A ray with a NaN in alpha or z gets an all-NaN row.  No atomics; every sum and product in a fixed order: bit-reproducible.
 #include "nnr_device.h"
 #include "nnr_kernels.h"
+#include "nnr_resample_row.h"
 #include "../../include/nnr.h"
 
 namespace nnr {
-
-constexpr int kResampleMaxN = 1024;     // C + F: the training limit on samples per ray
-constexpr int kSearchTrips = 10;        // ceil(log2 kResampleMaxN): an interval of at most 1023 elements closes in 10 halvings
-constexpr float kPdfFloor = 1e-5f;      // added to every bin's weight; also the guard on the CDF difference
-
-// how many leading elements of the non-decreasing arr[0, n) are <= x (LE) or < x (!LE); 1 <= n < kResampleMaxN
-template <bool LE>
-__device__ __forceinline__ int count_leading(const float* arr, int n, float x) {
-    int lo = 0, hi = n;
-#pragma unroll
-    for (int t = 0; t < kSearchTrips; ++t) {
-        const int mid = min((lo + hi) >> 1, n - 1);
-        const float v = arr[mid];
-        const bool go = LE ? (v <= x) : (v < x);      // false for a NaN on either side
-        const bool open = lo < hi;
-        lo = (open && go) ? mid + 1 : lo;
-        hi = (open && !go) ? mid : hi;
-    }
-    return lo;
-}
 
 struct ResampleArgs {
     const float *alpha, *z, *xi;   // (R,C), (R,C), (R,F) or null
@@ -86,94 +67,9 @@ __global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
     bad = __any(bad) != 0;
     __syncthreads();
 
-    // 2. transmittance and bin masses over contiguous runs of samples
-    {
-        const int per = (C + 63) >> 6;
-        const int i0 = min(lane * per, C), i1 = min(i0 + per, C);
-        float prod = 1.f;
-        for (int i = i0; i < i1; ++i) prod *= (1.f - out[i]) + kEpsT;
-        const float incl = wave_scan_mul(prod, lane);
-        float T = __shfl_up(incl, 1, 64);
-        if (lane == 0) T = 1.f;
-        for (int i = i0; i < i1; ++i) {
-            const float al = out[i];
-            if (i < C - 1) mm[i] = 0.5f * (zc[i] + zc[i + 1]);
-            out[i] = al * T + kPdfFloor;      // p_{i-1}; [0] and [C-1] are not bins and are never read again
-            T *= (1.f - al) + kEpsT;
-        }
-    }
-    __syncthreads();
-
-    // 3. CDF over contiguous runs of bins k in [0, C-2): p_k sits at out[k + 1]
-    {
-        const int nb = C - 2;
-        const int per = (nb + 63) >> 6;
-        const int k0 = min(lane * per, nb), k1 = min(k0 + per, nb);
-        float sum = 0.f;
-        for (int k = k0; k < k1; ++k) sum += out[k + 1];
-        float off = 0.f, total = 0.f;
-#pragma unroll
-        for (int t = 0; t < 64; ++t) {
-            const float v = __shfl(sum, t, 64);
-            if (t < lane) off += v;
-            total += v;
-        }
-        float acc = off;
-        for (int k = k0; k < k1; ++k) {
-            acc += out[k + 1];
-            cdf[k + 1] = acc / total;
-        }
-        if (lane == 0) cdf[0] = 0.f;
-    }
-    __syncthreads();
-
-    // 4. inverse CDF at the stratified u
-    {
-        const float* g_xi = a.xi ? a.xi + (int64_t)ray * F : nullptr;
-        const float n_fine = (float)F;
-        for (int j = lane; j < F; j += 64) {
-            const float xi = g_xi ? g_xi[j] : 0.5f;
-            const float u = ((float)j + xi) / n_fine;
-            const int i = count_leading<true>(cdf, C - 1, u);
-            const int below = max(i - 1, 0), above = min(i, C - 2);
-            const float cb = cdf[below], mb = mm[below], ma = mm[above];
-            float den = cdf[above] - cb;
-            if (den < kPdfFloor) den = 1.f;
-            float s = mb + (u - cb) / den * (ma - mb);
-            s = fminf(fmaxf(s, mb), ma);      // (fmaxf / fminf return the other operand for a NaN: s stays inside the bin)
-            fs[j] = s;
-        }
-    }
-    __syncthreads();
-
-    // 5. merge by rank (reads zc, fs; writes out, whose bin masses are dead)
-    for (int i = lane; i < C; i += 64) {
-        const float v = zc[i];
-        out[i + count_leading<false>(fs, F, v)] = v;
-    }
-    for (int j = lane; j < F; j += 64) {
-        const float v = fs[j];
-        out[j + count_leading<true>(zc, C, v)] = v;
-    }
-    __syncthreads();
-
-    // 6. stores
-    if (!live) return;
-    const float qnan = __builtin_nanf("");
-    float* g_out = a.z_all + (int64_t)ray * N;
-    if ((N & 3) == 0) {
-        for (int i = 4 * lane; i < N; i += 256) {
-            f32x4 v = *reinterpret_cast<const f32x4*>(out + i);
-            if (bad) v = f32x4{qnan, qnan, qnan, qnan};
-            *reinterpret_cast<f32x4*>(g_out + i) = v;
-        }
-    } else {
-        for (int i = lane; i < N; i += 64) g_out[i] = bad ? qnan : out[i];
-    }
-    if (a.fine) {
-        float* g_fine = a.fine + (int64_t)ray * F;
-        for (int j = lane; j < F; j += 64) g_fine[j] = bad ? qnan : fs[j];
-    }
+    // 2. to 6.: the row code shared with the fused proposal kernel (nnr_resample_row.h)
+    resample_row(zc, mm, cdf, fs, out, C, F, a.xi ? a.xi + (int64_t)ray * F : nullptr, a.z_all + (int64_t)ray * N,
+                 a.fine ? a.fine + (int64_t)ray * F : nullptr, lane, live, bad);
 }
 
 hipError_t launch_resample(int R, int C, int F, const float* alpha, const float* z, const float* xi, float* z_all, float* fine, hipStream_t st) {

@@ -10,6 +10,8 @@ alpha-compositing, and their backward.
 `rendering.num_fine: F` (default 0 = off; the reference has no counterpart) turns the render into NeRF's hierarchical sampling with one
 network: a coarse forward-only pass at the `num_points - outside_steps` samples above, `nnr.ops.resample` (nnr_resample.hip) for F more
 depths per ray from the coarse weights' inverse CDF, and the render proper -- the training path -- at the sorted union of both sets.
+`rendering.proposal: 'density'` (default 'render'; no reference counterpart either) replaces the coarse pass and the resampling launch by
+one launch of the fused proposal kernel (`nnr.ops.propose`, nnr_propose_f16.hip): the density of the coarse samples alone.
 
 `rendering.normal_loss: True` (reference :133-143; off by default, and no loss term of the reference consumes it) adds the
 normal-consistency vector `out['normal']`: second-order autograd through the MLP trunk for the 2 M surface points, in stock torch
@@ -196,17 +198,28 @@ class Renderer(nn.Module):
                   bf16=(str(cfg.get('mfma_dtype', 'fp32')).lower() == 'bf16'))   # rendering.mfma_dtype: fp32 (default) | bf16
         n_fine = int(cfg.get('num_fine', 0) or 0)    # rendering.num_fine: hierarchical sampling, 0 / absent = off (nothing below changes)
         if n_fine > 0:
+            proposal = cfg.get('proposal', None) or 'render'      # rendering.proposal (absent = 'render'; ignored without num_fine)
+            if proposal not in ('render', 'density'):
+                raise ValueError("rendering.proposal: expected 'render' or 'density', got %r" % (proposal,))
             if not pixels.is_cuda:
                 raise NotImplementedError("rendering.num_fine > 0 runs only on the GPU (HIP resampling kernel, nnr_resample.hip); there is no "
                                           "CPU hierarchical sampling -- set rendering.num_fine: 0 for CPU runs")
             # coarse pass (the inference forward: no stash, only alpha and z) -> nnr_resample -> the render proper at the sorted union of
             # the coarse depths and n_fine inverse-CDF samples of the coarse weights.  One network, trained at both sample sets; the
             # depths carry no gradient, pose / distortion gradients flow through pts_o / pts_d as before.
+            # rendering.proposal: 'render' (default) = that pair of launches; 'density' = one launch of the fused proposal kernel
+            # (nnr_propose_f16.hip through nnr.ops.propose): the coarse samples' density alone, always in the two-term fp16 products.
             xi = self._fine_draw(n_rays, n_fine, device) if (jitter is not None) else None   # after the jitter draw; else u at bin centres
-            with torch.no_grad():
-                _, _, alpha_c, z_c = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(), samples=True, **kw)
-            z_lo, z_hi = self._unit_tables(n_samples + n_fine, device)      # z = 0 + (1 - 0) * jitter: the kernels take the depths as given
-            jitter = _nnr_ops.resample(alpha_c, z_c, xi, n_fine)
+            if proposal == 'density':
+                z_all = _nnr_ops.propose(pts_o, pts_d, z_lo, z_hi, jitter, xi, n_fine, net.weights(), net.biases(), hidden=kw['hidden'],
+                                         dist_alpha=kw['dist_alpha'], relu_sigma=kw['relu_sigma'])
+                z_lo, z_hi = self._unit_tables(n_samples + n_fine, device)
+                jitter = z_all
+            else:      # today's path, as it was written
+                with torch.no_grad():
+                    _, _, alpha_c, z_c = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(), samples=True, **kw)
+                z_lo, z_hi = self._unit_tables(n_samples + n_fine, device)      # z = 0 + (1 - 0) * jitter: the kernels take the depths as given
+                jitter = _nnr_ops.resample(alpha_c, z_c, xi, n_fine)
         lazy_samples = not torch.is_grad_enabled()   # evaluation / visualisation: per-sample outputs only if somebody reads them
         rgb, dist_pred, alpha, z_val = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(),
                                                        samples=not lazy_samples, **kw)

@@ -418,3 +418,30 @@ def resample(alpha: torch.Tensor, z: torch.Tensor, xi: Optional[torch.Tensor], n
     fine = torch.empty(R, max(F, 0), dtype=torch.float32, device=dev) if return_fine else None
     L.check(L.load().nnr_resample(R, Cn, F, L.ptr(alpha), L.ptr(z), L.ptr(xi), L.ptr(z_all), L.ptr(fine), L.stream()), "nnr_resample")
     return (z_all, fine) if return_fine else z_all
+
+
+def propose(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor, jitter: Optional[torch.Tensor],
+            xi: Optional[torch.Tensor], n_fine: int, weights, biases, *, hidden: int, dist_alpha: bool, relu_sigma: bool, debug: bool = False):
+    """The proposal stage of hierarchical sampling in one launch (nnr_propose, include/nnr.h; rendering.proposal: 'density'): the inputs of the
+    coarse render_rays call without the view direction, xi (R,n_fine) in [0,1) or None (= 0.5) -> z_all (R, C + n_fine), what
+    resample(alpha, z, xi, n_fine) gives for the alpha, z of that coarse render -- from the density alone (no colour branch), with nothing per
+    sample written to HBM.  Always in the two-term fp16 products (split2_cfg), whatever the training step uses, as the phong renderer; the pack
+    is cached per parameter identity.  debug: (z_all, alpha_c (R,C), z_c (R,C), fine (R,n_fine)), the kernel's own intermediate rows.
+    Not differentiable (the depths carry no gradient).  3 <= C <= 256, C + n_fine <= 1024.  No host synchronisation."""
+    _require_gpu(pts_o)
+    R, Cn = pts_o.shape[0], z_lo.shape[0]
+    F = int(n_fine)
+    dev = pts_o.device
+    cfg = split2_cfg(R, Cn, hidden, dist_alpha=dist_alpha, relu_sigma=relu_sigma)
+    pts_o, pts_d = pts_o.detach().contiguous().float(), pts_d.detach().contiguous().float()
+    z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
+    jit = jitter.detach().contiguous().float().view(R, Cn) if jitter is not None else None
+    xi = xi.detach().contiguous().float().view(R, F) if xi is not None else None
+    packed = _packed_for(cfg, list(weights), list(biases))
+    f32 = dict(dtype=torch.float32, device=dev)
+    z_all = torch.empty(R, Cn + max(F, 0), **f32)
+    alpha_c, z_c, fine = ((torch.empty(R, Cn, **f32), torch.empty(R, Cn, **f32), torch.empty(R, max(F, 0), **f32)) if debug
+                          else (None, None, None))
+    L.check(L.load().nnr_propose(C.byref(cfg), F, L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), L.ptr(xi), L.ptr(packed),
+                                 L.ptr(z_all), L.ptr(alpha_c), L.ptr(z_c), L.ptr(fine), L.stream()), "nnr_propose")
+    return (z_all, alpha_c, z_c, fine) if debug else z_all

@@ -7,8 +7,10 @@ Reports (JSON lines, and DIR/time_resample.json), D = 256, fp32 (two-term fp16) 
   * resample_kernel at 1024 rays (64 coarse + 128 fine) and at 4096 rays (64 + 64), beside the coarse inference forward that feeds it
     (nnr.render_rays under no_grad with per-sample outputs) and a torch restatement of the definition in fp32 on the device -- the
     bar: the kernel takes no longer than the coarse forward of the same trace;
+  * propose_f16_kernel (rendering.proposal: 'density', nnr.ops.propose) on the same inputs at D = 256 and D = 128 -- the bar: no slower than
+    the coarse forward + resample_kernel of the same trace (at D = 128 beside a coarse forward of that width);
   * Trainer.train_step (front end, render, losses, backward, Adam for field / poses / distortion; rgb + depth losses) on a synthetic
-    scene of tools/scene_writer.py at 1024 rays: 64 + 128 against 192 uniform samples and 64 uniform samples.
+    scene of tools/scene_writer.py at 1024 rays: 64 + 128 in both proposal modes against 192 uniform samples and 64 uniform samples.
 The trace pass gives the per-kernel figures (the events include launch gaps); both go to DIR.  Exit status: the trace pass's."""
 import argparse
 import json
@@ -69,11 +71,11 @@ def _renderer(num_points, num_fine, hidden=256):
     return mdl.Renderer(net, cfg['rendering'], device=torch.device('cuda'))
 
 
-def _train_step_ms(scene_dir, n_samples, num_fine, steps=30):
+def _train_step_ms(scene_dir, n_samples, num_fine, steps=30, proposal=None):
     import dataloading as dl
     import train_scene
     cfg = train_scene.scene_cfg(scene_dir, "synthetic", n_rays=1024, n_samples=n_samples, hidden=256, num_fine=num_fine, aux=False,
-                                sample_rate=10 ** 6)
+                                sample_rate=10 ** 6, proposal=proposal)
     torch.manual_seed(0)
     loader, fields = dl.get_dataloader(cfg, mode="train", shuffle=True)
     trainer, _, _ = train_scene.build(cfg, torch.device('cuda'), fields["img"].N_imgs)
@@ -112,10 +114,17 @@ def workload(report):
             report("coarse_forward_" + tag, ms=_events(coarse, 20))
             report("resample_kernel_" + tag, ms=_events(lambda: ops.resample(alpha, z, xi, F), 50), bytes_moved=4 * R * (2 * C + F + C + F))
             report("torch_restatement_fp32_" + tag, ms=_events(lambda: torch_resample(alpha, z, xi, F), 5, warm=1))
+            for hidden, n in ((256, net), (128, _renderer(C, F, hidden=128).model)):      # the fused proposal kernel: one launch for the two above
+                fused = lambda: ops.propose(o, d, z_lo, z_hi, jit, xi, F, n.weights(), n.biases(), hidden=hidden, dist_alpha=False, relu_sigma=False)
+                report("propose_kernel_d%d_%s" % (hidden, tag), ms=_events(fused, 20))
+                if hidden == 128:
+                    c128 = lambda: nnr.render_rays(o, d, v, z_lo, z_hi, jit, n.weights(), n.biases(), samples=True, **dict(kw, hidden=128))
+                    report("coarse_forward_d128_" + tag, ms=_events(c128, 20))
     with tempfile.TemporaryDirectory() as scene_dir:
         scene_writer.write_scene(scene_dir, scene="synthetic", frames=8, size=(60, 80), seed=0)
-        for name, n_samples, num_fine in (("64+128", 64, 128), ("192_uniform", 192, 0), ("64_uniform", 64, 0)):
-            report("train_step_1024_" + name, ms=_train_step_ms(scene_dir, n_samples, num_fine))
+        for name, n_samples, num_fine, proposal in (("64+128", 64, 128, None), ("64+128_density", 64, 128, "density"), ("192_uniform", 192, 0, None),
+                                                    ("64_uniform", 64, 0, None)):
+            report("train_step_1024_" + name, ms=_train_step_ms(scene_dir, n_samples, num_fine, proposal=proposal))
 
 
 def main():

@@ -24,7 +24,7 @@ import torch
 
 
 def scene_cfg(path, scene, style="tanks", n_rays=1024, n_samples=128, hidden=256, resident=True, aux=True, resize_factor=None,
-              sample_rate=8, workers=0, mfma_dtype="fp32", num_fine=0):
+              sample_rate=8, workers=0, mfma_dtype="fp32", num_fine=0, proposal=None):
     """The keys configs/default.yaml + configs/Tanks/*.yaml (style 'tanks') or configs/LLFF/fern.yaml (style 'llff') would set."""
     llff = style == "llff"
     on = [1.0, 0.0] if aux else [0.0, 0.0]
@@ -39,7 +39,8 @@ def scene_cfg(path, scene, style="tanks", n_rays=1024, n_samples=128, hidden=256
                       "num_points": n_samples, "depth_range": [0.0, 1.0] if llff else [0.01, 10], "dist_alpha": llff,
                       "use_ray_dir": True, "normalise_ray": True, "normal_loss": False,
                       "sample_option": "ndc" if llff else "uniform", "outside_steps": 0, "mfma_dtype": mfma_dtype,
-                      **({"num_fine": int(num_fine)} if num_fine else {})},      # hierarchical sampling: num_points coarse + num_fine fine
+                      **({"num_fine": int(num_fine)} if num_fine else {}),
+                      **({"proposal": str(proposal)} if proposal else {})},      # hierarchical sampling: num_points coarse + num_fine fine
         "depth": {"type": "None"},
         "pose": {"learn_pose": True, "learn_R": True, "learn_t": True, "init_pose": False, "learn_focal": False},
         "distortion": {"learn_distortion": True, "fix_scaleN": True, "learn_scale": True, "learn_shift": True},
@@ -163,7 +164,7 @@ def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=No
         with tempfile.TemporaryDirectory() as tmp:
             novel = novel_view_eval(cfg, trainer.model, pose, field, device, eval_epochs, eval_dir or tmp, n_points=min(1024, n_rays))
     return {"novel_views": novel, "scene": scene, "style": style, "views": n_views, "image": [field.H, field.W], "rays_per_step": n_rays,
-            "samples_per_ray": cfg["rendering"]["num_points"], "fine_samples_per_ray": cfg["rendering"].get("num_fine", 0), "hidden": cfg["model"]["hidden_dim"], "epochs": epochs,
+            "samples_per_ray": cfg["rendering"]["num_points"], "fine_samples_per_ray": cfg["rendering"].get("num_fine", 0), "proposal": cfg["rendering"].get("proposal", "render"), "hidden": cfg["model"]["hidden_dim"], "epochs": epochs,
             "steps": it + 1, "loader": "resident" if cfg["dataloading"]["resident"] else "host(workers=%d)" % cfg["dataloading"]["n_workers"],
             "aux_losses": cfg["training"]["pc_weight"][0] != 0.0,
             "steps_per_s": steps_timed / t_loop if t_loop else None, "rays_per_s": steps_timed * n_rays / t_loop if t_loop else None,
@@ -185,6 +186,8 @@ def main():
     ap.add_argument("--no-aux", action="store_true")
     ap.add_argument("--bf16", action="store_true", help="rendering.mfma_dtype: bf16 (bf16 MFMA products, fp32 accumulation)")
     ap.add_argument("--num-fine", type=int, default=0, help="rendering.num_fine: fine samples per ray drawn from the coarse pass's weights (0 = off)")
+    ap.add_argument("--proposal", choices=("render", "density"), default=None,
+                    help="rendering.proposal (with --num-fine): 'render' = coarse forward + resampling launch (default), 'density' = the fused proposal kernel")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--eval-epochs", type=int, default=0, help="test-time pose optimisation epochs before scoring the held-out views")
     ap.add_argument("--eval-dir", default=None, help="where the rendered held-out frames go (default: a temporary directory)")
@@ -192,7 +195,7 @@ def main():
     a = ap.parse_args()
     res = run(a.path, a.scene, style=a.style, epochs=a.epochs, log_every=a.log_every, eval_epochs=a.eval_epochs, eval_dir=a.eval_dir, n_rays=a.rays, n_samples=a.samples,
               hidden=a.hidden, resident=not a.host_loader, aux=not a.no_aux, resize_factor=a.factor, workers=a.workers,
-              mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine)
+              mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine, proposal=a.proposal)
     print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
