@@ -197,6 +197,21 @@ int nnr_propose(const nnr_cfg* cfg, int32_t n_fine, const float* pts_o, const fl
                 const float* jitter, const float* xi, const float* packed, float* z_all, float* opt_alpha, float* opt_z, float* opt_fine,
                 void* stream);
 
+/* The raw density of the field on a regular grid in ONE launch (nnr_grid_f16.hip; model/geometry.py extracts a mesh from it): the trunk and the
+ * density head alone, the points made in the kernel, nothing per point read from HBM.  cfg: n_rays = nx ny nz, n_samples = 1, hidden 128 / 256,
+ * flags NNR_F_SPLIT3 | NNR_F_SPLIT2 (required, as for nnr_ray_march: the kernel evaluates in the two-term fp16 arithmetic, `packed` is that
+ * mode's buffer); NNR_F_TRAIN or NNR_F_BF16 -> NNR_E_UNSUPPORTED (NNR_F_DIST_ALPHA / NNR_F_RELU_SIGMA / NNR_F_WHITE_BG are ignored: the output
+ * is the density before its activation).  origin, step, dims = (nx, ny, nz): HOST arrays of three.  Voxel (ix, iy, iz) is the point
+ * p_c = origin_c + step_c * (float) i_c, the product and the sum rounded to fp32 one after the other (no fused multiply-add), so the same two
+ * fp32 operations on the host give the point's bits; a step may be negative or differ between the axes.  out: (nz, ny, nx) row-major (x
+ * fastest) fp32 on the device, the sigma_raw nnr_mlp_fwd writes for that point; NaN where an activation left fp16's range (NNR_F_SPLIT2).
+ * NNR_E_BADCFG for a null pointer, a dim < 1, an origin or step that is not finite, n_rays != nx ny nz or n_samples != 1;
+ * NNR_E_UNSUPPORTED for nx ny nz > 2^31 - 1, another hidden width or the flags above; NNR_E_ALIGN for `packed` not 16-byte or `out` not 4-byte
+ * aligned; all decided before any device work.  One launch, no host synchronisation, no atomics: bit-reproducible.
+ * (Added under ABI 8: a new function changes no existing signature or layout.) */
+int nnr_density_grid(const nnr_cfg* cfg, const float origin[3], const float step[3], const int32_t dims[3], const float* packed, float* out,
+                     void* stream);
+
 /* Individual stages, exported for profiling and bench.py's per-kernel roofline timing.  Same arguments
  * and workspace contract as the fused entry points above. */
 int nnr_mlp_fwd(const nnr_cfg* cfg, const float* pts_o, const float* pts_d, const float* view_d,

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <array>
@@ -783,6 +785,29 @@ int nnr_propose(const nnr_cfg* cfg, int32_t n_fine, const float* pts_o, const fl
     a.R = cfg->n_rays; a.C = cfg->n_samples; a.F = n_fine;
     a.flags = cfg->flags & (NNR_F_RELU_SIGMA | NNR_F_DIST_ALPHA);
     hipError_t e = launch_propose(cfg->hidden, a, (hipStream_t)stream);
+    return e == hipSuccess ? NNR_OK : hip_fail(e);
+}
+
+// the raw density on a regular grid in one launch (nnr_grid_f16.hip); origin, step and dims are HOST arrays, everything is decided before any device work
+int nnr_density_grid(const nnr_cfg* cfg, const float origin[3], const float step[3], const int32_t dims[3], const float* packed, float* out,
+                     void* stream) {
+    if (!cfg || !origin || !step || !dims || !packed || !out) return NNR_E_BADCFG;
+    if (cfg->hidden != 128 && cfg->hidden != 256) return NNR_E_UNSUPPORTED;
+    if ((cfg->flags & (NNR_F_TRAIN | NNR_F_BF16)) || !is_split2(cfg)) return NNR_E_UNSUPPORTED;
+    for (int c = 0; c < 3; ++c)
+        if (dims[c] < 1 || !std::isfinite(origin[c]) || !std::isfinite(step[c])) return NNR_E_BADCFG;
+    int64_t V = 1;
+    for (int c = 0; c < 3; ++c) {
+        V *= dims[c];      // (three factors below 2^31 each could pass 2^63: checked per factor)
+        if (V > INT32_MAX) return NNR_E_UNSUPPORTED;
+    }
+    if (cfg->n_rays != V || cfg->n_samples != 1) return NNR_E_BADCFG;
+    if (!aligned16(packed) || (reinterpret_cast<uintptr_t>(out) & 3u)) return NNR_E_ALIGN;
+    GridArgs a{};
+    a.packed = packed; a.out = out;
+    for (int c = 0; c < 3; ++c) { a.origin[c] = origin[c]; a.step[c] = step[c]; }
+    a.nx = (uint32_t)dims[0]; a.ny = (uint32_t)dims[1]; a.V = (uint32_t)V;
+    hipError_t e = launch_density_grid(cfg->hidden, a, (hipStream_t)stream);
     return e == hipSuccess ? NNR_OK : hip_fail(e);
 }
 

@@ -62,6 +62,16 @@ struct ProposeArgs {
 };
 constexpr int kProposeMaxC = 256;      // coarse samples per ray the kernel's LDS staging holds (include/nnr.h: nnr_propose)
 
+// the raw density on a regular grid (nnr_grid_f16.hip): voxel v = (ix, iy, iz), x fastest; p_c = origin_c + step_c * i_c
+struct GridArgs {
+    const float* packed;          // Layout<D, 3> (NNR_F_SPLIT3 | NNR_F_SPLIT2)
+    float* out;                   // (nz, ny, nx)
+    float origin[3], step[3];
+    uint32_t nx, ny, V;           // V = nx ny nz <= 2^31 - 1
+    uint32_t n_blocks;            // 128-voxel blocks (filled by the launcher)
+    int passes;                   // blocks per workgroup (filled by the launcher)
+};
+
 struct MlpDgradArgs {
     const float* packed;
     float* ws_dout4;        // (S_pad,4): d rgb_pre[3], d sigma_raw (rows >= S are zero-filled here)
@@ -260,6 +270,7 @@ hipError_t launch_march_finish(const float* state, float* d_out, int R, hipStrea
 // hierarchical sampling (nnr_resample.hip): alpha, z (R,C), xi (R,F) or null -> z_all (R,C+F), fine (R,F) or null
 hipError_t launch_resample(int R, int C, int F, const float* alpha, const float* z, const float* xi, float* z_all, float* fine, hipStream_t st);
 hipError_t launch_propose(int D, const ProposeArgs& a, hipStream_t st);                          // nnr_propose_f16.hip
+hipError_t launch_density_grid(int D, GridArgs a, hipStream_t st);                               // nnr_grid_f16.hip
 hipError_t launch_composite_fwd(const CompositeArgs& a, hipStream_t st);
 hipError_t launch_composite_bwd(const CompositeArgs& a, hipStream_t st);
 hipError_t launch_ray_reduce(const RayReduceArgs& a, hipStream_t st);

@@ -1,0 +1,318 @@
+"""Geometry export: the learned density as a volume, a surface-nets mesh of one of its level sets, and a PLY file.
+
+    density_volume   the raw density on a regular grid, in z-slabs of one launch of the fused grid kernel each (nnr.ops.density_grid)
+    level_for        the raw-density value of the phong renderer's occ = tau surface
+    surface_nets     volume -> (vertices, quads), plain torch, CPU or GPU tensors
+    extract_mesh     volume -> surface nets -> normals (nnr.ops.density_grad) -> colours (nnr.ops.mlp_points); GPU only
+    write_ply / read_ply
+
+Grid conventions, shared with the kernel: a volume is (nz, ny, nx), x fastest; grid point (ix, iy, iz) sits at origin + step * (ix, iy, iz)
+(fp32: the product rounded, then the sum).  There is no CPU volume path: the density comes from the HIP kernel or not at all."""
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from nnr import ops as _nnr_ops
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the volume
+# ----------------------------------------------------------------------------------------------------------------------
+def _resolution3(resolution):
+    r = (resolution,) * 3 if isinstance(resolution, int) else tuple(int(v) for v in resolution)
+    if len(r) != 3 or min(r) < 2:
+        raise ValueError("resolution: one int or (nx, ny, nz), every axis >= 2 grid points; got %r" % (resolution,))
+    return r
+
+
+def grid_of(lo, hi, resolution):
+    """(origin, step, dims) of the grid with `resolution` points per axis whose first point is `lo` and whose last is `hi` up to rounding:
+    step = (hi - lo) / (n - 1), rounded to fp32 once -- the grid is DEFINED by the fp32 origin and step, as the kernel sees them."""
+    dims = _resolution3(resolution)
+    origin = [float(np.float32(v)) for v in lo]
+    step = [float(np.float32((float(h) - float(l)) / (n - 1))) for l, h, n in zip(lo, hi, dims)]
+    return origin, step, dims
+
+
+def density_volume(renderer, lo, hi, resolution, slab=None):
+    """The raw density (before softplus / relu) of renderer.model on the grid grid_of(lo, hi, resolution) -> (nz, ny, nx) fp32 on the
+    model's device.  slab: the most z-layers per kernel launch (None: the whole volume in one launch), which bounds what a launch writes.
+    The slabbed result equals the one-call result bit for bit: a launch that starts at layer iz0 keeps the volume's step and takes
+    origin_z = fl(lo_z + fl(step_z * iz0)), the z the kernel forms for that layer in the one-call run, and covers only layers for which
+    its own fl(origin_z + fl(step_z * j)) is that run's fl(lo_z + fl(step_z * (iz0 + j))) -- checked on the host in fp32 (_slab_origins)."""
+    net = renderer.model
+    origin, step, dims = grid_of(lo, hi, resolution)
+    nx, ny, nz = dims
+    w, b = net.weights(), net.biases()
+    if slab is None or slab >= nz:
+        return _nnr_ops.density_grid(origin, step, dims, w, b, hidden=net.hidden_dim)
+    if slab < 1:
+        raise ValueError("slab: at least one z-layer per launch")
+    out = torch.empty(nz, ny, nx, dtype=torch.float32, device=w[0].device)
+    for iz0, n, oz in _slab_origins(origin[2], step[2], nz, int(slab)):
+        out[iz0:iz0 + n] = _nnr_ops.density_grid([origin[0], origin[1], oz], step, (nx, ny, n), w, b, hidden=net.hidden_dim)
+    return out
+
+
+def _layer_z(oz, sz, i):
+    """the kernel's z of layer i: fl(oz + fl(sz * (float) i)) in fp32"""
+    return np.float32(oz) + np.float32(sz) * np.float32(i)
+
+
+def _slab_origins(oz, sz, nz, slab):
+    """Cut layers [0, nz) into runs (iz0, n, origin_z) of at most `slab` layers such that a launch with origin_z and the volume's step forms
+    for its layer j exactly the one-call run's z of layer iz0 + j.  origin_z = fl(oz + fl(sz * iz0)) makes j = 0 exact by construction; the
+    other layers of the run are checked here on the host in the same fp32 arithmetic, and a run is cut short at the first layer where the
+    two roundings part (the next run then starts there, exact again).  With a step and an origin that are dyadic over the slab nothing is
+    ever cut; in general a few runs come out shorter than `slab`, none longer."""
+    runs, iz0 = [], 0
+    with np.errstate(over='ignore'):
+        while iz0 < nz:
+            o = _layer_z(oz, sz, iz0)
+            n = 1
+            while n < slab and iz0 + n < nz and _layer_z(o, sz, n) == _layer_z(oz, sz, iz0 + n):
+                n += 1
+            runs.append((iz0, n, float(o)))
+            iz0 += n
+    return runs
+
+
+def level_for(rendering_cfg, occ_activation, tau=0.5):
+    """The raw-density value at which the phong renderer's occupancy equals tau (its surface is occ = 0.5, model/rendering.py:
+    ray_marching).  OfficialStaticNerf's occupancy is occ = s(raw) with rendering.dist_alpha and 1 - exp(-s(raw)) without, s = softplus
+    (model.occ_activation: 'softplus') or relu; all four are non-decreasing in raw, so {occ > tau} = {raw > level}:
+
+        softplus               1 - exp(-softplus(raw)) = tau   ->   raw = log(tau / (1 - tau))      (0 at tau = 0.5)
+        softplus + dist_alpha  softplus(raw) = tau             ->   raw = log(exp(tau) - 1)
+        relu                   1 - exp(-relu(raw)) = tau       ->   raw = -log(1 - tau)
+        relu + dist_alpha      relu(raw) = tau                 ->   raw = tau
+
+    0 < tau (< 1 without dist_alpha)."""
+    tau = float(tau)
+    dist_alpha = bool(rendering_cfg['dist_alpha'])
+    if not tau > 0. or (not dist_alpha and not tau < 1.):
+        raise ValueError("tau = %r is not an occupancy the field can cross" % tau)
+    if occ_activation == 'softplus':
+        return math.log(math.expm1(tau)) if dist_alpha else math.log(tau / (1. - tau))
+    return tau if dist_alpha else -math.log1p(-tau)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# surface nets
+# ----------------------------------------------------------------------------------------------------------------------
+_CORNERS = [(k & 1, (k >> 1) & 1, (k >> 2) & 1) for k in range(8)]                              # corner k of a cell: (dx, dy, dz)
+_EDGES = [(a, a | bit) for bit in (1, 2, 4) for a in range(8) if not a & bit]                  # its 12 edges as corner pairs
+
+
+def surface_nets(volume, level, origin, step):
+    """Naive surface nets of {volume = level}: volume (nz, ny, nx) (any float dtype, CPU or GPU), grid point (ix, iy, iz) at
+    origin + step * (ix, iy, iz) -> (vertices (V,3) float32, quads (Q,4) int64) on the volume's device.  A corner is `inside` where
+    volume > level.
+      * one vertex per cell (8 neighbouring grid points) whose corners are not all on one side: the mean of the linearly interpolated
+        crossings on those of its 12 edges whose ends differ -- so it lies in the cell;
+      * one quad per grid edge whose ends differ and whose four neighbouring cells are inside the volume (edges on the volume's boundary
+        make none: the mesh of a surface that leaves the volume is open there), joining those cells' vertices; its normal (right-hand rule
+        over the corner order) points from the inside end to the outside end, whatever the signs of the steps;
+      * a cell with a NaN corner makes no vertex and no quad touches it.
+    No case table, no ambiguity handling: where a cell's corners alternate the mesh may be non-manifold, as surface nets are.
+    Deterministic: vertices in cell order (z, y, x: x fastest), quads by edge direction (x, y, z) and then in grid order of the edge.
+    The arithmetic is float64 whatever the input's dtype."""
+    vol = volume.detach().to(torch.float64)
+    dev = vol.device
+    nz, ny, nx = vol.shape
+    none = (torch.zeros(0, 3, dtype=torch.float32, device=dev), torch.zeros(0, 4, dtype=torch.int64, device=dev))
+    if min(nz, ny, nx) < 2:
+        return none
+    level = float(level)
+    ins = vol > level
+    nan = torch.isnan(vol)
+
+    def cells(t, dx, dy, dz):       # the corner (dx, dy, dz) of every cell
+        return t[dz:nz - 1 + dz, dy:ny - 1 + dy, dx:nx - 1 + dx]
+
+    n_in = sum(cells(ins, *c).to(torch.uint8) for c in _CORNERS)
+    bad = cells(nan, *_CORNERS[0])
+    for c in _CORNERS[1:]:
+        bad = bad | cells(nan, *c)
+    active = (n_in > 0) & (n_in < 8) & ~bad
+    cell = active.nonzero()                                    # (V,3): (cz, cy, cx), in cell order
+    V = cell.shape[0]
+    if V == 0:
+        return none
+    cz, cy, cx = cell.unbind(1)
+    val = torch.stack([vol[cz + dz, cy + dy, cx + dx] for dx, dy, dz in _CORNERS], 1)      # (V,8)
+    side = val > level
+    off = torch.tensor(_CORNERS, dtype=torch.float64, device=dev)
+    acc = torch.zeros(V, 3, dtype=torch.float64, device=dev)
+    cnt = torch.zeros(V, dtype=torch.float64, device=dev)
+    for a, b in _EDGES:
+        cross = side[:, a] != side[:, b]
+        t = torch.where(cross, (level - val[:, a]) / torch.where(cross, val[:, b] - val[:, a], torch.ones_like(cnt)), torch.zeros_like(cnt))
+        t = t.clamp(0., 1.)                                    # (an infinite corner value: the crossing at the finite end)
+        t = torch.where(torch.isnan(t), torch.full_like(t, 0.5), t)      # (both ends infinite)
+        acc += torch.where(cross.unsqueeze(1), off[a] + t.unsqueeze(1) * (off[b] - off[a]), torch.zeros_like(acc))
+        cnt += cross
+    local = acc / cnt.unsqueeze(1)
+    o = torch.tensor([float(v) for v in origin], dtype=torch.float64, device=dev)
+    s = torch.tensor([float(v) for v in step], dtype=torch.float64, device=dev)
+    vertices = (o + s * (cell.flip(1).to(torch.float64) + local)).to(torch.float32)
+
+    vid = torch.full((nz - 1, ny - 1, nx - 1), -1, dtype=torch.int64, device=dev)
+    vid[cz, cy, cx] = torch.arange(V, dtype=torch.int64, device=dev)
+    flip_all = (s[0] * s[1] * s[2]).item() < 0       # an odd number of negative steps mirrors the grid: the index-space winding is reversed
+    quads = []
+    # per direction: the edges with four cells around them, and those cells in right-hand order about the edge's +direction
+    # (x: y then z; y: z then x; z: x then y) -- (-,-), (+,-), (+,+), (-,+)
+    for axis in (0, 1, 2):
+        if axis == 0:       # edge (z, y, x)-(z, y, x+1), 1 <= z <= nz-2, 1 <= y <= ny-2
+            a, b = ins[1:nz - 1, 1:ny - 1, :-1], ins[1:nz - 1, 1:ny - 1, 1:]
+            ring = ((0, 0, 0), (0, 1, 0), (1, 1, 0), (1, 0, 0))           # (dz, dy, dx) into vid
+        elif axis == 1:     # edge (z, y, x)-(z, y+1, x), 1 <= z <= nz-2, 1 <= x <= nx-2
+            a, b = ins[1:nz - 1, :-1, 1:nx - 1], ins[1:nz - 1, 1:, 1:nx - 1]
+            ring = ((0, 0, 0), (1, 0, 0), (1, 0, 1), (0, 0, 1))
+        else:               # edge (z, y, x)-(z+1, y, x), 1 <= y <= ny-2, 1 <= x <= nx-2
+            a, b = ins[:-1, 1:ny - 1, 1:nx - 1], ins[1:, 1:ny - 1, 1:nx - 1]
+            ring = ((0, 0, 0), (0, 0, 1), (0, 1, 1), (0, 1, 0))
+        e = (a != b).nonzero()
+        if e.shape[0] == 0:
+            continue
+        i, j, k = e.unbind(1)
+        q = torch.stack([vid[i + dz, j + dy, k + dx] for dz, dy, dx in ring], 1)
+        rev = ~a[i, j, k]                                      # the inside end is the far one: the normal points down the axis
+        if flip_all:
+            rev = ~rev
+        q = torch.where(rev.unsqueeze(1), q[:, [0, 3, 2, 1]], q)
+        quads.append(q[(q >= 0).all(1)])                       # a NaN reads as outside: such an edge's cells have no vertex
+    quads = torch.cat(quads) if quads else none[1]
+    return vertices, quads
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the mesh
+# ----------------------------------------------------------------------------------------------------------------------
+@dataclass
+class Mesh:
+    vertices: torch.Tensor                       # (V,3) float32
+    quads: torch.Tensor                          # (Q,4) int64, normal by the right-hand rule from inside to outside
+    normals: Optional[torch.Tensor] = None       # (V,3) float32, unit, -grad(raw) / |grad(raw)| (NaN where the gradient vanishes)
+    colours: Optional[torch.Tensor] = None       # (V,3) float32 in [0,1]: the colour branch seen along -normal
+    level: float = 0.
+    origin: tuple = (0., 0., 0.)
+    step: tuple = (1., 1., 1.)
+    dims: tuple = (0, 0, 0)
+
+    def triangles(self):
+        """(2Q,3): every quad (a, b, c, d) split along its a-c diagonal into (a, b, c), (a, c, d), the quad's winding kept"""
+        q = self.quads
+        return torch.stack([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], 1).reshape(-1, 3)
+
+
+def extract_mesh(renderer, lo, hi, resolution, level=None, colour=True, slab=None, volume=None):
+    """The surface {raw density = level} of renderer.model inside the box [lo, hi] as a Mesh: density_volume -> surface_nets -> unit normals
+    -grad(raw) / |grad(raw)| at the vertices (nnr.ops.density_grad: the phong renderer's normals) -> vertex colours, the colour branch at
+    the vertex seen from outside along the normal (nnr.ops.mlp_points(v, view = -normal, split2=True), as the phong renderer's rgb_surf
+    with view = -ray).  level None: the phong renderer's surface, level_for(renderer.cfg, model.occ_activation).  volume: the result of
+    density_volume(renderer, lo, hi, resolution) where the caller has it already (None: computed here).  GPU only."""
+    net = renderer.model
+    w, b = net.weights(), net.biases()
+    if not w[0].is_cuda:
+        raise NotImplementedError("extract_mesh runs only on the GPU (HIP grid kernel, nnr_grid_f16.hip); there is no CPU volume path")
+    if level is None:
+        level = level_for(renderer.cfg, net.occ_activation)
+    origin, step, dims = grid_of(lo, hi, resolution)
+    with torch.no_grad():
+        vol = density_volume(renderer, lo, hi, resolution, slab=slab) if volume is None else volume
+        if tuple(vol.shape) != tuple(dims[::-1]):
+            raise ValueError("volume: shape %r is not the grid's (nz, ny, nx) = %r" % (tuple(vol.shape), tuple(dims[::-1])))
+        vertices, quads = surface_nets(vol, level, origin, step)
+        mesh = Mesh(vertices, quads, level=float(level), origin=tuple(origin), step=tuple(step), dims=tuple(dims))
+        if vertices.shape[0] == 0:
+            mesh.normals = torch.zeros_like(vertices)
+            mesh.colours = torch.zeros_like(vertices) if colour else None
+            return mesh
+        g = _nnr_ops.density_grad(vertices, w, b, net.hidden_dim).neg()
+        mesh.normals = g / g.norm(2, 1, keepdim=True)
+        if colour:
+            view = torch.nan_to_num(-mesh.normals)             # (a vanishing gradient: no direction to look along)
+            rgb, _ = _nnr_ops.mlp_points(vertices, view, w, b, hidden=net.hidden_dim, split2=True)
+            mesh.colours = rgb.clamp(0., 1.)
+    return mesh
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# PLY
+# ----------------------------------------------------------------------------------------------------------------------
+def write_ply(path, mesh):
+    """Binary little-endian PLY: vertices (x, y, z float32 [, nx, ny, nz float32] [, red, green, blue uint8 = round(255 colour)]) and
+    triangular faces (uint8 count, 3 int32 indices), two per quad (Mesh.triangles)."""
+    v = mesh.vertices.detach().cpu().numpy().astype('<f4')
+    fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+    cols = [v[:, 0], v[:, 1], v[:, 2]]
+    if mesh.normals is not None:
+        n = mesh.normals.detach().cpu().numpy().astype('<f4')
+        fields += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
+        cols += [n[:, 0], n[:, 1], n[:, 2]]
+    if mesh.colours is not None:
+        c = colours_u8(mesh.colours).cpu().numpy()
+        fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+        cols += [c[:, 0], c[:, 1], c[:, 2]]
+    rec = np.empty(v.shape[0], dtype=fields)
+    for (name, _), col in zip(fields, cols):
+        rec[name] = col
+    tri = mesh.triangles().detach().cpu().numpy()
+    if v.shape[0] > 2 ** 31 - 1:
+        raise ValueError("write_ply: the face indices are int32")
+    faces = np.empty(tri.shape[0], dtype=[('n', 'u1'), ('i', '<i4', (3,))])
+    faces['n'] = 3
+    faces['i'] = tri
+    names = {'<f4': 'float', 'u1': 'uchar'}
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % v.shape[0]]
+    header += ["property %s %s" % (names[t], name) for name, t in fields]
+    header += ["element face %d" % tri.shape[0], "property list uchar int vertex_indices", "end_header"]
+    with open(path, 'wb') as f:
+        f.write(("\n".join(header) + "\n").encode('ascii'))
+        f.write(rec.tobytes())
+        f.write(faces.tobytes())
+
+
+def colours_u8(colours):
+    """[0,1] floats -> the 8-bit values write_ply stores"""
+    return (colours.detach().clamp(0., 1.) * 255.).round().to(torch.uint8)
+
+
+def read_ply(path):
+    """What write_ply wrote -> dict(vertices (V,3) float32, normals (V,3) float32 or None, colours (V,3) uint8 or None, faces (F,3) int64),
+    numpy arrays.  Reads this module's files (binary little-endian, float / uchar vertex properties, triangles), not PLY in general."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode('ascii').split("\n")
+    if lines[0] != "ply" or lines[1] != "format binary_little_endian 1.0":
+        raise ValueError("%s: not a binary little-endian PLY file" % path)
+    types = {'float': '<f4', 'uchar': 'u1'}
+    fields, n_vert, n_face, element = [], 0, 0, None
+    for line in lines[2:]:
+        t = line.split()
+        if t[:1] == ['element']:
+            element = t[1]
+            if element == 'vertex':
+                n_vert = int(t[2])
+            elif element == 'face':
+                n_face = int(t[2])
+        elif t[:1] == ['property'] and element == 'vertex':
+            fields.append((t[2], types[t[1]]))
+    rec = np.frombuffer(data, dtype=fields, count=n_vert, offset=end)
+    faces = np.frombuffer(data, dtype=[('n', 'u1'), ('i', '<i4', (3,))], count=n_face, offset=end + rec.nbytes)
+    if n_face and not (faces['n'] == 3).all():
+        raise ValueError("%s: a face that is not a triangle" % path)
+    have = {name for name, _ in fields}
+
+    def cols(names, dtype):
+        return np.stack([rec[n] for n in names], 1).astype(dtype) if set(names) <= have else None
+
+    return dict(vertices=cols(('x', 'y', 'z'), np.float32), normals=cols(('nx', 'ny', 'nz'), np.float32),
+                colours=cols(('red', 'green', 'blue'), np.uint8), faces=faces['i'].astype(np.int64))
+

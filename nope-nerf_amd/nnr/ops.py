@@ -370,6 +370,28 @@ def ray_march(ray_o: torch.Tensor, ray_d: torch.Tensor, t_table: torch.Tensor, w
     return d
 
 
+def density_grid(origin, step, dims, weights, biases, *, hidden: int) -> torch.Tensor:
+    """The raw density (sigma_raw, before softplus / relu) on a regular grid in one launch of nnr_density_grid (include/nnr.h): origin, step
+    (three floats each), dims = (nx, ny, nz) -> (nz, ny, nx) fp32 on the weights' device.  Voxel (ix, iy, iz) is the point
+    origin + step * (ix, iy, iz), product and sum rounded to fp32 separately; the points are made in the kernel, nothing per point is read.
+    The value is mlp_points(p, ., split2=True)[1] at that point, bit for bit.  Always in the two-term fp16 products (split2_cfg); the pack is
+    cached per parameter identity, as for propose.  Not differentiable.  No host synchronisation."""
+    weights, biases = list(weights), list(biases)
+    _require_gpu(weights[0])
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) < 1 or nx * ny * nz > 2 ** 31 - 1:
+        raise ValueError("density_grid: dims %r: every dim >= 1 and at most 2^31 - 1 voxels in one call (model.geometry.density_volume "
+                         "walks a larger volume in slabs)" % ((nx, ny, nz),))
+    cfg = split2_cfg(nx * ny * nz, 1, hidden)
+    packed = _packed_for(cfg, weights, biases)
+    out = torch.empty(nz, ny, nx, dtype=torch.float32, device=weights[0].device)
+    o3 = (C.c_float * 3)(*[float(v) for v in origin])
+    s3 = (C.c_float * 3)(*[float(v) for v in step])
+    d3 = (C.c_int32 * 3)(nx, ny, nz)
+    L.check(L.load().nnr_density_grid(C.byref(cfg), o3, s3, d3, L.ptr(packed), L.ptr(out), L.stream()), "nnr_density_grid")
+    return out
+
+
 _P_DOUT4, _P_DPTS = 2, 3      # workspace planes (nnr_layout.h): the per-sample output gradient, the gradient of the sample's point
 
 

@@ -1,0 +1,127 @@
+"""CPU: the density-grid entry point of the C ABI (nnr_density_grid, added under ABI 8) -- version agreement, every error return reached
+with fake device pointers before anything is dereferenced or launched, and the Python wrapper's refusal of CPU weights."""
+import ctypes as C
+import os
+import re
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OK, E_BADCFG, E_UNSUPPORTED, E_ALIGN = 0, -1, -2, -3
+PACKED, OUT = C.c_void_p(0x10000), C.c_void_p(0x20000)      # fake device addresses
+INF, NAN = float("inf"), float("nan")
+
+
+def _lib():
+    from nnr import lib as L
+    return L, L.load()
+
+
+def _call(dims=(4, 5, 6), n_rays=None, n_samples=1, hidden=256, flags=None, origin=(0., 0., 0.), step=(1., 1., 1.), packed=PACKED, out=OUT,
+          null=()):
+    L, lib = _lib()
+    flags = (L.NNR_F_SPLIT3 | L.NNR_F_SPLIT2) if flags is None else flags
+    cfg = L.Cfg(dims[0] * dims[1] * dims[2] if n_rays is None else n_rays, n_samples, hidden, flags)
+    o3, s3, d3 = (C.c_float * 3)(*origin), (C.c_float * 3)(*step), (C.c_int32 * 3)(*dims)
+    args = dict(cfg=C.byref(cfg), origin=o3, step=s3, dims=d3, packed=packed, out=out)
+    for n in null:
+        args[n] = None
+    return lib.nnr_density_grid(args["cfg"], args["origin"], args["step"], args["dims"], args["packed"], args["out"], None)
+
+
+def test_abi_version_stays_8_and_the_entry_point_is_everywhere():
+    L, lib = _lib()
+    hdr = open(os.path.join(ROOT, "include", "nnr.h")).read()
+    assert lib.nnr_abi_version() == L.ABI_VERSION == int(re.search(r"#define NNR_ABI_VERSION (\d+)", hdr).group(1)) == 8
+    assert "nnr_density_grid" in L.EXPORTS and re.search(r"\bint nnr_density_grid\(", hdr) and hasattr(lib, "nnr_density_grid")
+    assert len(lib.nnr_density_grid.argtypes) == 7
+    assert len(L.EXPORTS) == 50
+
+
+@pytest.mark.parametrize("name", ["cfg", "origin", "step", "dims", "packed", "out"])
+def test_null_pointers_are_rejected(name):
+    assert _call(null=(name,)) == E_BADCFG
+
+
+@pytest.mark.parametrize("dims", [(0, 5, 6), (4, 0, 6), (4, 5, 0), (-1, 5, 6), (4, 5, -2 ** 31)])
+def test_a_dim_below_one_is_rejected(dims):
+    assert _call(dims=dims, n_rays=1) == E_BADCFG
+
+
+def test_a_dim_below_one_is_reported_before_the_volume_size():
+    assert _call(dims=(2 ** 31 - 1, 2, 0), n_rays=1) == E_BADCFG
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+@pytest.mark.parametrize("bad", [INF, -INF, NAN])
+def test_non_finite_origin_or_step_is_rejected(axis, bad):
+    v = [0.5, 0.5, 0.5]
+    v[axis] = bad
+    assert _call(origin=v) == E_BADCFG
+    assert _call(step=v) == E_BADCFG
+
+
+@pytest.mark.parametrize("n_rays", [0, 119, 121, -120])
+def test_n_rays_must_be_the_voxel_count(n_rays):
+    assert _call(dims=(4, 5, 6), n_rays=n_rays) == E_BADCFG
+    assert _call(dims=(4, 5, 6), n_rays=120, packed=C.c_void_p(0x10004)) == E_ALIGN      # (120 itself passes this check)
+
+
+@pytest.mark.parametrize("n_samples", [0, 2, -1])
+def test_n_samples_must_be_one(n_samples):
+    assert _call(n_samples=n_samples) == E_BADCFG
+
+
+@pytest.mark.parametrize("dims", [(2 ** 16, 2 ** 15, 1), (2 ** 11, 2 ** 10, 2 ** 10), (2 ** 31 - 1, 2, 1), (2 ** 31 - 1, 2 ** 31 - 1, 2 ** 31 - 1)])
+def test_more_than_int32_voxels_is_unsupported(dims):
+    assert _call(dims=dims, n_rays=2 ** 31 - 1) == E_UNSUPPORTED
+
+
+def test_the_largest_volume_passes_the_size_check():
+    assert _call(dims=(2 ** 31 - 1, 1, 1), packed=C.c_void_p(0x10004)) == E_ALIGN
+
+
+def test_hidden_width_is_checked():
+    assert _call(hidden=192) == E_UNSUPPORTED
+    assert _call(hidden=64) == E_UNSUPPORTED
+    assert _call(hidden=128, out=C.c_void_p(0x20002)) == E_ALIGN
+
+
+def test_flags_are_checked():
+    """The kernel exists in the two-term fp16 arithmetic only, forward-only; the rendering switches do not matter to the raw density and are
+    accepted (they reach the alignment check behind the flag check)."""
+    L, _ = _lib()
+    s2 = L.NNR_F_SPLIT3 | L.NNR_F_SPLIT2
+    for flags in (0, L.NNR_F_SPLIT3, L.NNR_F_SPLIT2, s2 | L.NNR_F_TRAIN, s2 | L.NNR_F_BF16, L.NNR_F_BF16):
+        assert _call(flags=flags) == E_UNSUPPORTED, flags
+    for flags in (s2, s2 | L.NNR_F_DIST_ALPHA, s2 | L.NNR_F_RELU_SIGMA, s2 | L.NNR_F_WHITE_BG):
+        assert _call(flags=flags, packed=C.c_void_p(0x10008)) == E_ALIGN, flags
+
+
+def test_misaligned_pointers_are_rejected():
+    for addr in (0x10001, 0x10002, 0x10004, 0x10008, 0x1000c):      # packed: the kernel's 16-byte accesses
+        assert _call(packed=C.c_void_p(addr)) == E_ALIGN, hex(addr)
+    for addr in (0x20001, 0x20002, 0x20003):                        # out: one float per voxel
+        assert _call(out=C.c_void_p(addr)) == E_ALIGN, hex(addr)
+
+
+def test_ops_density_grid_raises_on_cpu_weights():
+    import model as mdl
+    from nnr import ops
+    net = mdl.OfficialStaticNerf({'model': {'hidden_dim': 128, 'pos_enc_levels': 10, 'dir_enc_levels': 4, 'occ_activation': 'softplus'},
+                                  'rendering': {'white_background': False, 'dist_alpha': False}})
+    with pytest.raises(RuntimeError):
+        ops.density_grid((0., 0., 0.), (.1, .1, .1), (4, 4, 4), net.weights(), net.biases(), hidden=128)
+
+
+def test_the_build_holds_the_grid_kernel_to_no_scratch():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("nnr_build", os.path.join(ROOT, "nope-nerf_amd", "csrc", "build.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.SCRATCH_LIMIT["15grid_f16_kernelI"] == 0 and ("nnr_grid_f16.hip", ()) in b.SOURCES
+    remark = "remark: Function Name: _ZN3nnr15grid_f16_kernelILi256EEEvNS_8GridArgsE\nremark:     ScratchSize [bytes/lane]: %d\n"
+    b.check_resources(remark % 0, "grid")
+    with pytest.raises(RuntimeError, match="scratch"):
+        b.check_resources(remark % 16, "grid")
