@@ -31,7 +31,9 @@ SOURCES = [("nnr_wgrad.hip", ()), ("nnr_wgrad.hip", ("NNR_WGRAD_F16_TU=1",)), ("
 def _obj_name(src, defines):
     tag = "".join("_" + d.split("=")[0].lower().replace("nnr_", "") + d.split("=")[1] for d in defines)
     return os.path.splitext(src)[0] + tag + ".o"
-SPLIT2_ONLY = ["nnr_split2.h", "nnr_trunk_f16.h", "nnr_trunk_f16.inc"]      # included by the fp16-term kernels (the `_f16` units) only: touching them does not rebuild the rest (minutes per unit)
+SPLIT2_ONLY = ["nnr_split2.h", "nnr_trunk_f16.h", "nnr_trunk_f16.inc"]      # included by the fp16-term kernels (the `_f16` units: forward, input gradient, march, proposal, grid) only: touching them does not rebuild the rest (minutes per unit)
+DENSITY_ONLY = ["nnr_density_setup_f16.inc", "nnr_density_pass_f16.inc"]      # the density-only pass of the march, proposal and grid kernels: touching it rebuilds those three units, not the forward and input-gradient `_f16` units
+DENSITY_UNITS = ("nnr_march_f16.hip", "nnr_propose_f16.hip", "nnr_grid_f16.hip")
 ROW_ONLY = ["nnr_resample_row.h"]      # the row code of hierarchical sampling: nnr_resample.hip and nnr_propose_f16.hip
 FWD_ONLY = ["nnr_mlp_fwd_common.h"]      # included by nnr_mlp_fwd.hip and, through nnr_trunk_f16.h, by the `_f16` units
 HEADERS = ["nnr_layout.h", "nnr_device.h", "nnr_kernels.h", "nnr_mlp_bf16.h", "nnr_split.h", os.path.join("..", "..", "include", "nnr.h")]
@@ -106,6 +108,16 @@ def build_variant(name, defines, only=None):
     return out
 
 
+def own_headers(src):
+    """The headers beyond HEADERS that a source includes (file names in csrc/): what else makes its objects stale."""
+    own = SPLIT2_ONLY + FWD_ONLY if "_f16" in src else FWD_ONLY if src == "nnr_mlp_fwd.hip" else []
+    if src in DENSITY_UNITS:
+        own = own + DENSITY_ONLY
+    if src in ("nnr_resample.hip", "nnr_propose_f16.hip"):
+        own = own + ROW_ONLY
+    return own
+
+
 LAST_BUILD = {"compiled": [], "reused": [], "linked": False}      # what the newest build() call did (printed by __graft_entry__.build())
 
 
@@ -116,8 +128,7 @@ def build(force=False, verbose=False):
     jobs = []
     for src, defines in SOURCES:
         obj = os.path.join(OUT_DIR, _obj_name(src, defines))
-        own = [os.path.join(HERE, h) for h in (SPLIT2_ONLY + FWD_ONLY if "_f16" in src else FWD_ONLY if src == "nnr_mlp_fwd.hip" else [])]
-        own += [os.path.join(HERE, h) for h in (ROW_ONLY if src in ("nnr_resample.hip", "nnr_propose_f16.hip") else [])]
+        own = [os.path.join(HERE, h) for h in own_headers(src)]
         if force or _stale(obj, [os.path.join(HERE, src)] + hdrs + own):
             jobs.append([hipcc] + FLAGS + ["-D" + d for d in defines] + ["-c", os.path.join(HERE, src), "-o", obj])
 

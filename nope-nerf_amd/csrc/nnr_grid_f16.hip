@@ -1,8 +1,8 @@
 // nnr_grid_f16.hip -- the raw density of OfficialStaticNerf on a regular grid in one launch (include/nnr.h: nnr_density_grid; DESIGN.md
-// section 11): the input of the mesh extraction (model/geometry.py).  The third kernel on the shared trunk text, built as march_f16_kernel's
-// flat mode (nnr_march_f16.hip): four waves of 32 points per pass, position encoding, the eight trunk layers (nnr_trunk_f16.h, TRAIN = false)
-// and the density head in the two-term fp16 arithmetic, nothing of the colour branch and no view direction; the weight stream stops in
-// front of the colour panels.
+// section 11): the input of the mesh extraction (model/geometry.py).  Four waves of 32 points per pass; the pass is the density-only pass
+// shared with march_f16_kernel and propose_f16_kernel (nnr_density_setup_f16.inc: LDS and the weight stream, which stops in front of the
+// colour panels; nnr_density_pass_f16.inc: position encoding, the eight trunk layers and the density head in the two-term fp16 arithmetic,
+// nothing of the colour branch and no view direction).  This file holds the voxel's point and the store.
 //   * points: nothing per point is read from HBM.  Voxel v (linear, x fastest) = (ix, iy, iz), coordinate c of its point
 //     p_c = origin_c + step_c * i_c, the product and the sum rounded separately (grid_coord: no contraction): fp32 code on the host that
 //     multiplies and then adds gets the same bits.
@@ -27,20 +27,8 @@ __device__ __forceinline__ float grid_coord(float origin, float step, uint32_t i
 
 template <int D>
 __global__ __launch_bounds__(256, 1) void grid_f16_kernel(GridArgs a) {
-    using L = Layout<D, 3>;
-    using Pipe = Split2PipeT<false>;
-    constexpr int kRingF4 = kNBuf * Pipe::F4;
-    constexpr int DT = L::DT, HT = L::HT;
-    const int lane0 = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-
-    constexpr int kPark = kWavesPerBlock * 8 * 64;   // per wave 8 16-byte slots per lane: the packed terms of posenc
-    __shared__ __attribute__((aligned(16))) f32x4 smem[kRingF4 + kPark + (L::table_floats + 3) / 4];
-    float* const ltab = reinterpret_cast<float*>(smem + kRingF4 + kPark);
-    for (int i = threadIdx.x; i < L::table_floats; i += 256) ltab[i] = a.packed[L::bias_base + i];
-    __syncthreads();
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    Pipe pipe{reinterpret_cast<const f32x4*>(a.packed) + wave_u * (Pipe::PW * 64), smem, wave_u, lane0, L::fwd_panel0(F_RGBH_F)};
+    constexpr int kDensityExtraF4 = 0;      // nothing of its own in LDS
+#include "nnr_density_setup_f16.inc"
     // this workgroup's 128-voxel blocks: [block0, block0 + n_pass) (the launcher's grid leaves every workgroup at least one)
     const uint32_t block0 = blockIdx.x * (uint32_t)a.passes;
     const uint32_t left = a.n_blocks - block0;
@@ -68,43 +56,7 @@ __global__ __launch_bounds__(256, 1) void grid_f16_kernel(GridArgs a) {
     const float py = grid_coord(a.origin[1], a.step[1], iy);
     const float pz = grid_coord(a.origin[2], a.step[2], iz);
 
-    constexpr int HR = 16 * HT;
-    constexpr int NP = HR / 2;
-
-    uint32_t eh[16], em[16];      // gamma_10(p): 63 -> 64 values = 16 pairs
-    {
-        float e[32];
-#pragma unroll
-        for (int r = 0; r < 32; ++r) e[r] = enc_register(r, half, kPosReal, px, py, pz);
-        split2_all(eh, em, [&](int r) { return e[r]; });
-    }
-    const float* bias = ltab - L::bias_base;
-
-    uint32_t ph[8 * DT], pm[8 * DT];
-    f32x16 accA[HT], accB[HT];
-    float mx = 0.f, mxa = 0.f;           // running maximum of the activations (the fp16 range check)
-    float sg0 = 0.f, sg1 = 0.f;          // density head: this lane's share of w_sigma . h8
-    {   // the trunk, nothing of the training side
-        constexpr bool TRAIN = false;
-        const TrunkStash st{};
-        auto xh = [](int) -> const char* { return nullptr; };
-        auto p0 = [&](int part) { return L::fwd_panel0(part); };
-#include "nnr_trunk_f16.inc"
-    }
-    {   // hidden 8, half B, finished in plain code as in the march kernel: the same products as unit_fwd_infer and the head's other half
-        const float inv = inv_scale<L>(bias, 7);
-#pragma unroll
-        for (int u = 0; u < NP; ++u) {
-            const int r = 2 * u;
-            const float x0 = relu1(accB[r >> 4][r & 15] * inv), x1 = relu1(accB[(r + 1) >> 4][(r + 1) & 15] * inv);
-            mx = fmaxf(mx, fmaxf(x0, x1));
-            const f32x2 w2 = *reinterpret_cast<const f32x2*>(bias + L::wsig_off + half * (16 * DT) + 2 * NP + r);
-            sg0 = fmaf(w2[0], x0, sg0);
-            sg1 = fmaf(w2[1], x1, sg1);
-        }
-    }
-    const float sg = sg0 + sg1;
-    float raw = sg + __shfl_xor(sg, 32, 64) + bias[L::bias_off(8)];
+#include "nnr_density_pass_f16.inc"
     if (left_f16_range(mx)) raw = __uint_as_float(0x7fc00000u);
     if (half == 0 && v < a.V) a.out[v] = raw;
     pipe.next_pass(pass + 2 < n_pass);

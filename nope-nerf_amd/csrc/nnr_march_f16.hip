@@ -3,7 +3,9 @@
 // two-term fp16 arithmetic of nnr_mlp_fwd_f16.hip (NNR_F_SPLIT3 | NNR_F_SPLIT2, Layout<D, 3>, three fp16 MFMA terms per product, fp32 accumulation,
 // weights through the DMA-fed LDS ring).  It shares that kernel's trunk (nnr_trunk_f16.h, TRAIN = false) and has nothing of its direction
 // encoding and colour GEMMs; the weight stream stops in front of the colour panels (n_panels = fwd_panel0(F_RGBH_F)), so a workgroup's
-// passes wrap around the trunk's panels only.
+// passes wrap around the trunk's panels only.  The LDS carve-up and the stream (nnr_density_setup_f16.inc) and the pass from the point to the
+// raw density (nnr_density_pass_f16.inc) are text shared with propose_f16_kernel and grid_f16_kernel; this file holds the march's own points
+// and what it does with the density.
 //
 // Two modes, one kernel:
 //   * ray mode (MarchArgs::flat == 0): one wave walks one ray's n_steps proposals d_j = d_far * t_j in passes of 32 samples (the workgroup four
@@ -35,20 +37,8 @@ __device__ __forceinline__ float secant_pred(f32x4 st) {
 
 template <int D>
 __global__ __launch_bounds__(256, 1) void march_f16_kernel(MarchArgs a) {
-    using L = Layout<D, 3>;
-    using Pipe = Split2PipeT<false>;
-    constexpr int kRingF4 = kNBuf * Pipe::F4;
-    constexpr int DT = L::DT, HT = L::HT;
-    const int lane0 = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-
-    constexpr int kPark = kWavesPerBlock * 8 * 64;   // per wave 8 16-byte slots per lane: the packed terms of posenc
-    __shared__ __attribute__((aligned(16))) f32x4 smem[kRingF4 + kPark + (L::table_floats + 3) / 4];
-    float* const ltab = reinterpret_cast<float*>(smem + kRingF4 + kPark);
-    for (int i = threadIdx.x; i < L::table_floats; i += 256) ltab[i] = a.packed[L::bias_base + i];
-    __syncthreads();
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    Pipe pipe{reinterpret_cast<const f32x4*>(a.packed) + wave_u * (Pipe::PW * 64), smem, wave_u, lane0, L::fwd_panel0(F_RGBH_F)};
+    constexpr int kDensityExtraF4 = 0;      // nothing of its own in LDS
+#include "nnr_density_setup_f16.inc"
     const int n_pass = a.flat ? 1 : (a.n_steps + kChunk - 1) / kChunk;
     pipe.more = n_pass > 1;
     pipe.start();
@@ -98,44 +88,7 @@ __global__ __launch_bounds__(256, 1) void march_f16_kernel(MarchArgs a) {
     const float py = __fadd_rn(ro[1], __fmul_rn(rd[1], d));
     const float pz = __fadd_rn(ro[2], __fmul_rn(rd[2], d));
 
-    constexpr int HR = 16 * HT;
-    constexpr int NP = HR / 2;
-
-    uint32_t eh[16], em[16];      // gamma_10(p): 63 -> 64 values = 16 pairs
-    {
-        float e[32];
-#pragma unroll
-        for (int r = 0; r < 32; ++r) e[r] = enc_register(r, half, kPosReal, px, py, pz);
-        split2_all(eh, em, [&](int r) { return e[r]; });
-    }
-    const float* bias = ltab - L::bias_base;
-
-    uint32_t ph[8 * DT], pm[8 * DT];
-    f32x16 accA[HT], accB[HT];
-    float mx = 0.f, mxa = 0.f;           // running maximum of the activations (the fp16 range check)
-    float sg0 = 0.f, sg1 = 0.f;          // density head: this lane's share of w_sigma . h8
-    {   // the trunk, nothing of the training side
-        constexpr bool TRAIN = false;
-        const TrunkStash st{};
-        auto xh = [](int) -> const char* { return nullptr; };
-        auto p0 = [&](int part) { return L::fwd_panel0(part); };
-#include "nnr_trunk_f16.inc"
-    }
-    {   // hidden 8, half B: no colour GEMM to hide it under -- finished here in plain code (the units' inline asm reads accumulators with no
-        // hazard cover of its own; here the compiler sees the MFMA results it reads), the same products as unit_fwd_infer and the head's other half
-        const float inv = inv_scale<L>(bias, 7);
-#pragma unroll
-        for (int u = 0; u < NP; ++u) {
-            const int r = 2 * u;
-            const float x0 = relu1(accB[r >> 4][r & 15] * inv), x1 = relu1(accB[(r + 1) >> 4][(r + 1) & 15] * inv);
-            mx = fmaxf(mx, fmaxf(x0, x1));
-            const f32x2 w2 = *reinterpret_cast<const f32x2*>(bias + L::wsig_off + half * (16 * DT) + 2 * NP + r);
-            sg0 = fmaf(w2[0], x0, sg0);
-            sg1 = fmaf(w2[1], x1, sg1);
-        }
-    }
-    const float sg = sg0 + sg1;
-    float raw = sg + __shfl_xor(sg, 32, 64) + bias[L::bias_off(8)];
+#include "nnr_density_pass_f16.inc"
     if (left_f16_range(mx)) raw = __uint_as_float(0x7fc00000u);
     const float val = march_val(raw, a.flags);
 

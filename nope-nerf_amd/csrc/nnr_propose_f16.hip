@@ -1,9 +1,10 @@
 // nnr_propose_f16.hip -- the proposal stage of hierarchical sampling in one launch (rendering.proposal: 'density'; include/nnr.h: nnr_propose;
-// DESIGN.md section 10): ray in, the sorted row of C coarse and F fine depths out, nothing per sample through HBM.  Two kernels' text joined:
-//   * the passes are march_f16_kernel's ray mode (nnr_march_f16.hip): one wave walks one ray's C coarse samples in passes of 32 (the workgroup
-//     four rays), position encoding, the eight trunk layers (nnr_trunk_f16.h, TRAIN = false) and the density head in the two-term fp16
-//     arithmetic, nothing of the colour branch and no view direction; the weight stream stops in front of the colour panels.  The depths are
-//     the forward kernel's (nnr_mlp_fwd_f16.hip: z = z_lo + (z_hi - z_lo) jitter, p = o + d z, rounded op by op).  Lanes of half 0 leave the
+// DESIGN.md section 10): ray in, the sorted row of C coarse and F fine depths out, nothing per sample through HBM.  Two stages:
+//   * the passes are the density-only pass shared with march_f16_kernel and grid_f16_kernel (nnr_density_setup_f16.inc: LDS and the weight
+//     stream, with this kernel's staging rows between park and tables; nnr_density_pass_f16.inc: position encoding, the eight trunk layers and
+//     the density head in the two-term fp16 arithmetic), walked as the march's ray mode: one wave walks one ray's C coarse samples in passes
+//     of 32 (the workgroup four rays).  The depths are the forward kernel's (nnr_mlp_fwd_f16.hip: z = z_lo + (z_hi - z_lo) jitter,
+//     p = o + d z, rounded op by op).  Lanes of half 0 leave the
 //     sample's raw density and depth in the wave's LDS staging row.  Every pass runs for every wave (the four waves share the weight stream
 //     and its barriers): a wave past the last ray repeats the last ray and stores nothing; samples j >= C of the last pass are clamped loads
 //     and are not staged.
@@ -22,22 +23,9 @@ namespace nnr {
 
 template <int D>
 __global__ __launch_bounds__(256, 1) void propose_f16_kernel(ProposeArgs a) {
-    using L = Layout<D, 3>;
-    using Pipe = Split2PipeT<false>;
-    constexpr int kRingF4 = kNBuf * Pipe::F4;
-    constexpr int DT = L::DT, HT = L::HT;
-    const int lane0 = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-
-    constexpr int kPark = kWavesPerBlock * 8 * 64;   // per wave 8 16-byte slots per lane: the packed terms of posenc
-    constexpr int kStageF4 = kWavesPerBlock * 2 * kProposeMaxC / 4;      // per wave the raw densities and the depths of its ray
+    constexpr int kDensityExtraF4 = kWavesPerBlock * 2 * kProposeMaxC / 4;      // per wave the raw densities and the depths of its ray
+#include "nnr_density_setup_f16.inc"
     static_assert(kWavesPerBlock * (2 * kProposeMaxC + 2 * kResampleMaxN) <= kRingF4 * 4, "the rows of the resampling stage fit in the weight ring");
-    __shared__ __attribute__((aligned(16))) f32x4 smem[kRingF4 + kPark + kStageF4 + (L::table_floats + 3) / 4];
-    float* const ltab = reinterpret_cast<float*>(smem + kRingF4 + kPark + kStageF4);
-    for (int i = threadIdx.x; i < L::table_floats; i += 256) ltab[i] = a.packed[L::bias_base + i];
-    __syncthreads();
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    Pipe pipe{reinterpret_cast<const f32x4*>(a.packed) + wave_u * (Pipe::PW * 64), smem, wave_u, lane0, L::fwd_panel0(F_RGBH_F)};
     const int C = a.C, F = a.F;
     const int n_pass = (C + kChunk - 1) / kChunk;
     pipe.more = n_pass > 1;
@@ -70,43 +58,7 @@ __global__ __launch_bounds__(256, 1) void propose_f16_kernel(ProposeArgs a) {
     const float py = __fadd_rn(ro[1], __fmul_rn(rd[1], z));
     const float pz = __fadd_rn(ro[2], __fmul_rn(rd[2], z));
 
-    constexpr int HR = 16 * HT;
-    constexpr int NP = HR / 2;
-
-    uint32_t eh[16], em[16];      // gamma_10(p): 63 -> 64 values = 16 pairs
-    {
-        float e[32];
-#pragma unroll
-        for (int r = 0; r < 32; ++r) e[r] = enc_register(r, half, kPosReal, px, py, pz);
-        split2_all(eh, em, [&](int r) { return e[r]; });
-    }
-    const float* bias = ltab - L::bias_base;
-
-    uint32_t ph[8 * DT], pm[8 * DT];
-    f32x16 accA[HT], accB[HT];
-    float mx = 0.f, mxa = 0.f;           // running maximum of the activations (the fp16 range check)
-    float sg0 = 0.f, sg1 = 0.f;          // density head: this lane's share of w_sigma . h8
-    {   // the trunk, nothing of the training side
-        constexpr bool TRAIN = false;
-        const TrunkStash st{};
-        auto xh = [](int) -> const char* { return nullptr; };
-        auto p0 = [&](int part) { return L::fwd_panel0(part); };
-#include "nnr_trunk_f16.inc"
-    }
-    {   // hidden 8, half B, finished in plain code as in the march kernel: the same products as unit_fwd_infer and the head's other half
-        const float inv = inv_scale<L>(bias, 7);
-#pragma unroll
-        for (int u = 0; u < NP; ++u) {
-            const int r = 2 * u;
-            const float x0 = relu1(accB[r >> 4][r & 15] * inv), x1 = relu1(accB[(r + 1) >> 4][(r + 1) & 15] * inv);
-            mx = fmaxf(mx, fmaxf(x0, x1));
-            const f32x2 w2 = *reinterpret_cast<const f32x2*>(bias + L::wsig_off + half * (16 * DT) + 2 * NP + r);
-            sg0 = fmaf(w2[0], x0, sg0);
-            sg1 = fmaf(w2[1], x1, sg1);
-        }
-    }
-    const float sg = sg0 + sg1;
-    float raw = sg + __shfl_xor(sg, 32, 64) + bias[L::bias_off(8)];
+#include "nnr_density_pass_f16.inc"
     const bool finite_p = fabsf(px) < __uint_as_float(0x7f800000u) && fabsf(py) < __uint_as_float(0x7f800000u) && fabsf(pz) < __uint_as_float(0x7f800000u);
     if (left_f16_range(mx) || !finite_p) raw = __uint_as_float(0x7fc00000u);
     if (half == 0 && j < C) {

@@ -1,6 +1,8 @@
 // nnr_trunk_f16.h, nnr_trunk_f16.inc -- the trunk of OfficialStaticNerf (model/official_nerf.py:60-66: hidden 1 to 8, the skip connection into hidden 5) in
-// the two-term fp16 arithmetic of nnr_split2.h, ONCE, for the kernels that evaluate it: mlp_fwd_f16_kernel (nnr_mlp_fwd_f16.hip: inference
-// and training, the colour branch behind it) and march_f16_kernel (nnr_march_f16.hip: TRAIN = false, nothing of the colour branch).
+// the two-term fp16 arithmetic of nnr_split2.h, ONCE, for the four kernels that evaluate it: mlp_fwd_f16_kernel (nnr_mlp_fwd_f16.hip: inference
+// and training, the colour branch behind it) and the three density-only kernels, TRAIN = false and nothing of the colour branch: march_f16_kernel
+// (nnr_march_f16.hip), propose_f16_kernel (nnr_propose_f16.hip) and grid_f16_kernel (nnr_grid_f16.hip), which include the trunk through their
+// one shared pass (nnr_density_pass_f16.inc, behind nnr_density_setup_f16.inc).
 //   * between the layers a lane holds the PACKED TERMS of the activations (pair p -> ph[p], pm[p]: 32 bits per value, as many registers as the
 //     fp32 values took), made once by the epilogue unit that finishes the pair; a GEMM row is 3 MT MFMAs + 3 MT fragment refills and nothing else;
 //   * an epilogue unit = read the accumulator pair, undo the weight scale (one packed multiply by 1 / s_w: the accumulator started at s_w bias),
@@ -8,8 +10,8 @@
 //     [hidden 8: two FMAs of the density head], split;
 //   * every D-wide layer runs as two half-output passes, the epilogue of one pass hidden in the MFMA stream of the next.
 // Where the weight stream ends is the caller's pipe (n_panels: L::fwd_panels, or L::fwd_panel0(F_RGBH_F) without the colour branch).
-// This header: what the trunk's text and its two callers use.  nnr_trunk_f16.inc: the trunk itself, a block of statements that a kernel includes
-// inside its pass loop.  Text, not a function template: as a forceinlined template over the register arrays (by reference) everything inlined and
+// This header: what the trunk's text and its four consumers use.  nnr_trunk_f16.inc: the trunk itself, a block of statements that the forward
+// kernel and the density-only pass include inside the pass loop.  Text, not a function template: as a forceinlined template over the register arrays (by reference) everything inlined and
 // the resources stayed, but hipcc 7.2 reduced the panel arithmetic of the `#pragma unroll 1` layer loops differently and the forward kernels'
 // listings changed (tools/isa_listing.py); included as text they are the listings of the kernel that held this text itself.
 #pragma once

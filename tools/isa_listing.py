@@ -1,11 +1,13 @@
 """Device listings of csrc units as hashes: did a source change alter what a kernel executes?
 
     python tools/isa_listing.py OUT.json [--keep DIR] SUBSTRING [SUBSTRING ...]
+    python tools/isa_listing.py --compare A.json B.json
 
 Compiles every entry of csrc/build.py's SOURCES whose file name contains one of the substrings with build.FLAGS plus
 `--cuda-device-only -S`, drops comment-only lines and the per-translation-unit `__hip_cuid_` symbol, and writes per unit the SHA-256 of
 the rest and its v_mfma count, per kernel the SHA-256 of its body and hipcc's kernel-resource-usage figures.  Two runs (before / after a
-refactor) are compared with any JSON diff; --keep leaves the filtered listings in DIR for a textual one.  No GPU needed."""
+refactor) are compared with --compare: it prints every unit and kernel that only one file has or whose hash or figures differ, and exits
+non-zero if there is one; --keep leaves the filtered listings in DIR for a textual diff.  No GPU needed."""
 import hashlib
 import json
 import os
@@ -54,7 +56,39 @@ def unit(job, keep):
     return name, {"sha256": sha(lines), "lines": len(lines), "v_mfma": sum("v_mfma" in l for l in lines), "kernels": kernels}
 
 
+def compare(path_a, path_b):
+    """Print what differs between two listings; the number of differences."""
+    with open(path_a) as f:
+        a = json.load(f)
+    with open(path_b) as f:
+        b = json.load(f)
+    diffs = []
+    if a["flags"] != b["flags"]:
+        diffs.append("flags: %s != %s" % (a["flags"], b["flags"]))
+
+    def walk(what, x, y):      # a unit or a kernel: its own figures, then its kernels
+        if x is None or y is None:
+            diffs.append("%s: only in %s" % (what, path_b if x is None else path_a))
+            return
+        for key in sorted((set(x) | set(y)) - {"kernels"}):
+            if x.get(key) != y.get(key):
+                diffs.append("%s: %s %s != %s" % (what, key, x.get(key), y.get(key)))
+        kx, ky = x.get("kernels", {}), y.get("kernels", {})
+        for k in sorted(set(kx) | set(ky)):
+            walk(what + " " + k, kx.get(k), ky.get(k))
+
+    for u in sorted(set(a["units"]) | set(b["units"])):
+        walk(u, a["units"].get(u), b["units"].get(u))
+    for d in diffs:
+        print(d)
+    n_kernels = sum(len(u.get("kernels", {})) for u in a["units"].values())
+    print("%d units, %d kernels: %s" % (len(a["units"]), n_kernels, "%d differences" % len(diffs) if diffs else "equal"))
+    return len(diffs)
+
+
 def main(argv):
+    if argv and argv[0] == "--compare":
+        sys.exit(1 if compare(argv[1], argv[2]) else 0)
     keep = None
     if "--keep" in argv:
         keep = argv.pop(argv.index("--keep") + 1)
