@@ -24,7 +24,7 @@ SOURCES = [("nnr_wgrad.hip", ()), ("nnr_wgrad.hip", ("NNR_WGRAD_F16_TU=1",)), ("
            ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256",)), ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=128",)),
            ("nnr_mlp_fwd_bf16.hip", ()), ("nnr_mlp_dgrad_bf16.hip", ()), ("nnr_mlp_fwd.hip", ()), ("nnr_mlp_dgrad.hip", ()),
-           ("nnr_api.cpp", ()), ("nnr_pack.hip", ()), ("nnr_wgrad_bf16.hip", ()), ("nnr_composite.hip", ()), ("nnr_resample.hip", ()),
+           ("nnr_api.cpp", ()), ("nnr_wgrad_plan.cpp", ()), ("nnr_pack.hip", ()), ("nnr_wgrad_bf16.hip", ()), ("nnr_composite.hip", ()), ("nnr_resample.hip", ()),
            ("nnr_camera.hip", ()), ("nnr_pointcloud.hip", ()), ("nnr_aux.hip", ()), ("nnr_randperm.hip", ()), ("nnr_optim.hip", ())]
 
 
@@ -36,6 +36,7 @@ DENSITY_ONLY = ["nnr_density_setup_f16.inc", "nnr_density_pass_f16.inc"]      # 
 DENSITY_UNITS = ("nnr_march_f16.hip", "nnr_propose_f16.hip", "nnr_grid_f16.hip")
 ROW_ONLY = ["nnr_resample_row.h"]      # the row code of hierarchical sampling: nnr_resample.hip and nnr_propose_f16.hip
 FWD_ONLY = ["nnr_mlp_fwd_common.h"]      # included by nnr_mlp_fwd.hip and, through nnr_trunk_f16.h, by the `_f16` units
+PLAN_ONLY = ["nnr_wgrad_plan.h"]      # the host planners' header (no kernel includes it): nnr_api.cpp and nnr_wgrad_plan.cpp
 HEADERS = ["nnr_layout.h", "nnr_device.h", "nnr_kernels.h", "nnr_mlp_bf16.h", "nnr_split.h", os.path.join("..", "..", "include", "nnr.h")]
 # -pragma-unroll-threshold: the MLP kernels are straight-line code by construction (every `#pragma unroll` loop must unroll fully, or
 # the register arrays they index fall back to scratch memory).  LLVM caps `#pragma unroll` at 16 K instructions per loop; one GEMM part
@@ -115,6 +116,8 @@ def own_headers(src):
         own = own + DENSITY_ONLY
     if src in ("nnr_resample.hip", "nnr_propose_f16.hip"):
         own = own + ROW_ONLY
+    if src in ("nnr_api.cpp", "nnr_wgrad_plan.cpp"):
+        own = own + PLAN_ONLY
     return own
 
 

@@ -120,15 +120,25 @@ def _give_workspace(cfg: L.Cfg, device, ws: torch.Tensor):
         pool.append(ws)
 
 
+def _plan_blob(cfg: L.Cfg) -> bytes:
+    """The weight-gradient plan of cfg as nnr_plan_build writes it (include/nnr.h), on the host."""
+    lib = L.load()
+    raw = C.create_string_buffer(lib.nnr_plan_bytes(C.byref(cfg)))
+    L.check(lib.nnr_plan_build(C.byref(cfg), C.cast(raw, C.c_void_p)), "nnr_plan_build")
+    return raw.raw
+
+
+def _plan_counts(cfg: L.Cfg):
+    nj, nw = C.c_int32(0), C.c_int32(0)
+    L.check(L.load().nnr_plan_counts(C.byref(cfg), C.byref(nj), C.byref(nw)), "nnr_plan_counts")
+    return nj.value, nw.value
+
+
 def _plan_for(cfg: L.Cfg, device) -> torch.Tensor:
     key = _cfg_key(cfg, device)
     plan = _plan_cache.get(key)
     if plan is None:
-        lib = L.load()
-        nbytes = lib.nnr_plan_bytes(C.byref(cfg))
-        host = np.zeros(nbytes, dtype=np.uint8)
-        L.check(lib.nnr_plan_build(C.byref(cfg), host.ctypes.data_as(C.c_void_p)), "nnr_plan_build")
-        plan = torch.from_numpy(host).to(device)
+        plan = torch.from_numpy(np.frombuffer(_plan_blob(cfg), dtype=np.uint8).copy()).to(device)
         _plan_cache[key] = plan
     return plan
 
@@ -136,34 +146,24 @@ def _plan_for(cfg: L.Cfg, device) -> torch.Tensor:
 def plan_jobs(cfg: L.Cfg, with_waves: bool = False):
     """Host copy of the weight-gradient plan as a list of WgradJob (for tests / DESIGN inspection); with_waves also
     returns the wave_first table (wave w runs jobs [wave_first[w], wave_first[w+1]))."""
-    lib = L.load()
-    nj, nw = C.c_int32(0), C.c_int32(0)
-    L.check(lib.nnr_plan_counts(C.byref(cfg), C.byref(nj), C.byref(nw)), "nnr_plan_counts")
-    nbytes = lib.nnr_plan_bytes(C.byref(cfg))
-    assert nbytes >= nj.value * C.sizeof(L.WgradJob) + 4 * (nw.value + 1 + 1)      # + n_heads and the head list (split 0 of every tile)
-    raw = (C.c_uint8 * nbytes)()
-    L.check(lib.nnr_plan_build(C.byref(cfg), C.cast(raw, C.c_void_p)), "nnr_plan_build")
-    jobs = list((L.WgradJob * nj.value).from_buffer_copy(raw, 0))
+    (nj, nw), raw = _plan_counts(cfg), _plan_blob(cfg)
+    assert len(raw) >= nj * C.sizeof(L.WgradJob) + 4 * (nw + 1 + 1)      # + n_heads and the head list (split 0 of every tile)
+    jobs = list((L.WgradJob * nj).from_buffer_copy(raw, 0))
     if not with_waves:
         return jobs
-    first = list((C.c_int32 * (nw.value + 1)).from_buffer_copy(raw, nj.value * C.sizeof(L.WgradJob)))
+    first = list((C.c_int32 * (nw + 1)).from_buffer_copy(raw, nj * C.sizeof(L.WgradJob)))
     return jobs, first
 
 
 def plan_bf16(cfg: L.Cfg):
     """Host copy of the bf16-mode weight-gradient plan: (jobs, block_first, outputs) -- for tests / DESIGN inspection."""
-    lib = L.load()
-    nj, nw = C.c_int32(0), C.c_int32(0)
-    L.check(lib.nnr_plan_counts(C.byref(cfg), C.byref(nj), C.byref(nw)), "nnr_plan_counts")
-    nbytes = lib.nnr_plan_bytes(C.byref(cfg))
-    raw = (C.c_uint8 * nbytes)()
-    L.check(lib.nnr_plan_build(C.byref(cfg), C.cast(raw, C.c_void_p)), "nnr_plan_build")
-    n_blocks = nw.value // 4
-    o1 = nj.value * C.sizeof(L.WgradJobB)
+    (nj, nw), raw = _plan_counts(cfg), _plan_blob(cfg)
+    n_blocks = nw // 4
+    o1 = nj * C.sizeof(L.WgradJobB)
     o2 = o1 + 4 * (n_blocks + 1)
-    n_out = (nbytes - o2) // C.sizeof(L.WgradOutB)
-    assert o2 + n_out * C.sizeof(L.WgradOutB) == nbytes
-    jobs = list((L.WgradJobB * nj.value).from_buffer_copy(raw, 0))
+    n_out = (len(raw) - o2) // C.sizeof(L.WgradOutB)
+    assert o2 + n_out * C.sizeof(L.WgradOutB) == len(raw)
+    jobs = list((L.WgradJobB * nj).from_buffer_copy(raw, 0))
     first = list((C.c_int32 * (n_blocks + 1)).from_buffer_copy(raw, o1))
     outs = list((L.WgradOutB * n_out).from_buffer_copy(raw, o2))
     return jobs, first, outs

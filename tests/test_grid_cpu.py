@@ -146,6 +146,9 @@ def test_the_build_rebuilds_the_density_units_for_the_shared_pass_only():
     for src in sorted({s for s, _ in b.SOURCES}):
         assert ("nnr_resample_row.h" in b.own_headers(src)) == (src in ("nnr_resample.hip", "nnr_propose_f16.hip")), src
         assert all(os.path.exists(os.path.join(csrc, h)) for h in b.own_headers(src)), src
+        # the host planners' header belongs to the two host units alone, and is no common header: touching it rebuilds no kernel
+        assert ("nnr_wgrad_plan.h" in b.own_headers(src)) == (src in ("nnr_api.cpp", "nnr_wgrad_plan.cpp")), src
+    assert ("nnr_wgrad_plan.cpp", ()) in b.SOURCES and "nnr_wgrad_plan.h" not in b.HEADERS
     # the three kernels include both shared files, and the trunk's text through the pass alone
     for src in density:
         with open(os.path.join(csrc, src)) as f:

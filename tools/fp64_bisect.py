@@ -84,9 +84,7 @@ def hip(params, pts_o, pts_d, view, z_lo, z_hi, jitter, d_rgb, d_dist, D, produc
         L.check(lib.nnr_mlp_dgrad(C.byref(cfg), L.ptr(packed), L.ptr(ws), st), "mlp_dgrad")
         gw, gb = [torch.zeros_like(w) for w in w_d], [torch.zeros_like(b) for b in b_d]
         gs = L.params_struct(gw, gb)
-        host = np.zeros(lib.nnr_plan_bytes(C.byref(cfg)), dtype=np.uint8)
-        L.check(lib.nnr_plan_build(C.byref(cfg), host.ctypes.data_as(C.c_void_p)), "plan")
-        plan = torch.from_numpy(host).to(dev)
+        plan = ops._plan_for(cfg, dev)
         L.check(lib.nnr_mlp_wgrad(C.byref(cfg), L.ptr(packed), C.byref(gs), L.ptr(plan), L.ptr(ws), st), "wgrad")
         d_o, d_d, d_v = (torch.empty(R, 3, device=dev) for _ in range(3))
         L.check(lib.nnr_ray_reduce(C.byref(cfg), L.ptr(d_o), L.ptr(d_d), L.ptr(d_v), L.ptr(ws), st), "ray_reduce")
