@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/nnr.h"
+#include "../../include/nnr_geometry.h"
 #include "nnr_device.h"
 #include "nnr_kernels.h"
 #include "nnr_layout.h"
@@ -39,7 +40,7 @@ int check_cfg(const nnr_cfg* c) {
     return NNR_OK;
 }
 
-// what the density-only kernels (march, proposal, grid) share: width 128 / 256, two-term mode (which excludes NNR_F_BF16), not training
+// what the density-only kernels (march, proposal, grid, bricks) share: width 128 / 256, two-term mode (which excludes NNR_F_BF16), not training
 int check_density_cfg(const nnr_cfg* c) {
     return ((c->hidden != 128 && c->hidden != 256) || (c->flags & NNR_F_TRAIN) || !is_split2(c)) ? NNR_E_UNSUPPORTED : NNR_OK;
 }
@@ -366,6 +367,23 @@ int nnr_density_grid(const nnr_cfg* cfg, const float origin[3], const float step
     for (int c = 0; c < 3; ++c) { a.origin[c] = origin[c]; a.step[c] = step[c]; }
     a.nx = (uint32_t)dims[0]; a.ny = (uint32_t)dims[1]; a.V = (uint32_t)V;
     return launched(launch_density_grid(cfg->hidden, a, (hipStream_t)stream));
+}
+
+// the raw density in a list of 8 x 8 x 8 bricks of a regular grid in one launch (nnr_bricks_f16.hip; include/nnr_geometry.h); origin and step are
+// HOST arrays, `bricks` is on the device and is never read here: everything is decided before any device work
+int nnr_density_bricks(const nnr_cfg* cfg, const float origin[3], const float step[3], const int32_t* bricks, int32_t n_bricks,
+                       const float* packed, float* out, void* stream) {
+    if (!cfg || !origin || !step || !bricks || !packed || !out || n_bricks < 1) return NNR_E_BADCFG;
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(origin[c]) || !std::isfinite(step[c])) return NNR_E_BADCFG;
+    const int64_t V = 512 * (int64_t)n_bricks;
+    if (check_density_cfg(cfg) != NNR_OK || V > INT32_MAX) return NNR_E_UNSUPPORTED;
+    if (cfg->n_rays != V || cfg->n_samples != 1) return NNR_E_BADCFG;
+    if (!aligned(packed, 16) || !aligned(bricks, 4) || !aligned(out, 4)) return NNR_E_ALIGN;
+    BricksArgs a{};
+    a.packed = packed; a.bricks = bricks; a.out = out;
+    for (int c = 0; c < 3; ++c) { a.origin[c] = origin[c]; a.step[c] = step[c]; }
+    return launched(launch_density_bricks(cfg->hidden, a, n_bricks, (hipStream_t)stream));
 }
 
 int nnr_composite_bwd(const nnr_cfg* cfg, const float* d_rgb, const float* d_dist, float* ws, void* stream) {

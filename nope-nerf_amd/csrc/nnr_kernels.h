@@ -72,6 +72,16 @@ struct GridArgs {
     int passes;                   // blocks per workgroup (filled by the launcher)
 };
 
+// the raw density in 8 x 8 x 8 bricks of a regular grid (nnr_bricks_f16.hip): brick (bx, by, bz) holds the grid points i_c = 8 b_c + l_c, l_c in 0..7
+struct BricksArgs {
+    const float* packed;          // Layout<D, 3> (NNR_F_SPLIT3 | NNR_F_SPLIT2)
+    const int32_t* bricks;        // (B,3): (bx, by, bz)
+    float* out;                   // (B, 8, 8, 8): [lz][ly][lx]
+    float origin[3], step[3];
+    uint32_t n_blocks;            // 128-voxel blocks = 4 B (filled by the launcher)
+    int passes;                   // blocks per workgroup (filled by the launcher)
+};
+
 struct MlpDgradArgs {
     const float* packed;
     float* ws_dout4;        // (S_pad,4): d rgb_pre[3], d sigma_raw (rows >= S are zero-filled here)
@@ -271,6 +281,7 @@ hipError_t launch_march_finish(const float* state, float* d_out, int R, hipStrea
 hipError_t launch_resample(int R, int C, int F, const float* alpha, const float* z, const float* xi, float* z_all, float* fine, hipStream_t st);
 hipError_t launch_propose(int D, const ProposeArgs& a, hipStream_t st);                          // nnr_propose_f16.hip
 hipError_t launch_density_grid(int D, GridArgs a, hipStream_t st);                               // nnr_grid_f16.hip
+hipError_t launch_density_bricks(int D, BricksArgs a, int n_bricks, hipStream_t st);             // nnr_bricks_f16.hip
 hipError_t launch_composite_fwd(const CompositeArgs& a, hipStream_t st);
 hipError_t launch_composite_bwd(const CompositeArgs& a, hipStream_t st);
 hipError_t launch_ray_reduce(const RayReduceArgs& a, hipStream_t st);

@@ -4,6 +4,9 @@
     level_for        the raw-density value of the phong renderer's occ = tau surface
     surface_nets     volume -> (vertices, quads), plain torch, CPU or GPU tensors
     extract_mesh     volume -> surface nets -> normals (nnr.ops.density_grad) -> colours (nnr.ops.mlp_points); GPU only
+    extract_mesh_refined   a coarse volume -> the 8^3 bricks of a 2, 4 or 8 times finer grid around the coarse cells the surface crosses
+                     (refined_grid, select_cells, bricks_for; nnr.ops.density_bricks) -> surface nets on those bricks alone
+                     (sparse_surface_nets) -> normals and colours in chunks: the dense fine mesh restricted to what the coarse pass sees
     write_ply / read_ply
 
 Grid conventions, shared with the kernel: a volume is (nz, ny, nx), x fastest; grid point (ix, iy, iz) sits at origin + step * (ix, iy, iz)
@@ -107,6 +110,26 @@ _CORNERS = [(k & 1, (k >> 1) & 1, (k >> 2) & 1) for k in range(8)]              
 _EDGES = [(a, a | bit) for bit in (1, 2, 4) for a in range(8) if not a & bit]                  # its 12 edges as corner pairs
 
 
+def _cell_vertices(val, cell, level, o, s):
+    """The vertices of active cells, one row per cell: val (V,8) float64, the corner values in _CORNERS order; cell (V,3) int64, (cx, cy, cz);
+    o, s the grid's origin and step as float64 tensors -> (V,3) float32.  The arithmetic of surface_nets and sparse_surface_nets, row by row:
+    a cell's vertex depends on its own row alone, so the two agree bit for bit on a cell they both hold."""
+    V, dev = val.shape[0], val.device
+    side = val > level
+    off = torch.tensor(_CORNERS, dtype=torch.float64, device=dev)
+    acc = torch.zeros(V, 3, dtype=torch.float64, device=dev)
+    cnt = torch.zeros(V, dtype=torch.float64, device=dev)
+    for a, b in _EDGES:
+        cross = side[:, a] != side[:, b]
+        t = torch.where(cross, (level - val[:, a]) / torch.where(cross, val[:, b] - val[:, a], torch.ones_like(cnt)), torch.zeros_like(cnt))
+        t = t.clamp(0., 1.)                                    # (an infinite corner value: the crossing at the finite end)
+        t = torch.where(torch.isnan(t), torch.full_like(t, 0.5), t)      # (both ends infinite)
+        acc += torch.where(cross.unsqueeze(1), off[a] + t.unsqueeze(1) * (off[b] - off[a]), torch.zeros_like(acc))
+        cnt += cross
+    local = acc / cnt.unsqueeze(1)
+    return (o + s * (cell.to(torch.float64) + local)).to(torch.float32)
+
+
 def surface_nets(volume, level, origin, step):
     """Naive surface nets of {volume = level}: volume (nz, ny, nx) (any float dtype, CPU or GPU), grid point (ix, iy, iz) at
     origin + step * (ix, iy, iz) -> (vertices (V,3) float32, quads (Q,4) int64) on the volume's device.  A corner is `inside` where
@@ -144,21 +167,9 @@ def surface_nets(volume, level, origin, step):
         return none
     cz, cy, cx = cell.unbind(1)
     val = torch.stack([vol[cz + dz, cy + dy, cx + dx] for dx, dy, dz in _CORNERS], 1)      # (V,8)
-    side = val > level
-    off = torch.tensor(_CORNERS, dtype=torch.float64, device=dev)
-    acc = torch.zeros(V, 3, dtype=torch.float64, device=dev)
-    cnt = torch.zeros(V, dtype=torch.float64, device=dev)
-    for a, b in _EDGES:
-        cross = side[:, a] != side[:, b]
-        t = torch.where(cross, (level - val[:, a]) / torch.where(cross, val[:, b] - val[:, a], torch.ones_like(cnt)), torch.zeros_like(cnt))
-        t = t.clamp(0., 1.)                                    # (an infinite corner value: the crossing at the finite end)
-        t = torch.where(torch.isnan(t), torch.full_like(t, 0.5), t)      # (both ends infinite)
-        acc += torch.where(cross.unsqueeze(1), off[a] + t.unsqueeze(1) * (off[b] - off[a]), torch.zeros_like(acc))
-        cnt += cross
-    local = acc / cnt.unsqueeze(1)
     o = torch.tensor([float(v) for v in origin], dtype=torch.float64, device=dev)
     s = torch.tensor([float(v) for v in step], dtype=torch.float64, device=dev)
-    vertices = (o + s * (cell.flip(1).to(torch.float64) + local)).to(torch.float32)
+    vertices = _cell_vertices(val, cell.flip(1), level, o, s)
 
     vid = torch.full((nz - 1, ny - 1, nx - 1), -1, dtype=torch.int64, device=dev)
     vid[cz, cy, cx] = torch.arange(V, dtype=torch.int64, device=dev)
@@ -203,6 +214,8 @@ class Mesh:
     origin: tuple = (0., 0., 0.)
     step: tuple = (1., 1., 1.)
     dims: tuple = (0, 0, 0)
+    refine: int = 1                              # extract_mesh_refined: origin, step and dims are the FINE grid's, `refine` times the coarse one
+    n_bricks: int = 0                            # ... and the 8^3 bricks of it that were evaluated
 
     def triangles(self):
         """(2Q,3): every quad (a, b, c, d) split along its a-c diagonal into (a, b, c), (a, c, d), the quad's winding kept"""
@@ -240,6 +253,232 @@ def extract_mesh(renderer, lo, hi, resolution, level=None, colour=True, slab=Non
             rgb, _ = _nnr_ops.mlp_points(vertices, view, w, b, hidden=net.hidden_dim, split2=True)
             mesh.colours = rgb.clamp(0., 1.)
     return mesh
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the refined mesh: the fine grid evaluated in sparse bricks
+# ----------------------------------------------------------------------------------------------------------------------
+BRICK = 8      # grid points per brick and axis (nnr_bricks_f16.hip)
+
+
+def refined_grid(lo, hi, resolution, refine):
+    """The coarse grid of `resolution` points per axis over [lo, hi] and the `refine` (2, 4 or 8) times finer one that shares its points ->
+    (origin, step_c, dims_c, step_f, dims_f).  dims_f = (n - 1) refine + 1; step_f = (hi - lo) / (n_f - 1), rounded to fp32 once, and
+    step_c = refine * step_f, exact (a power of two): coarse point k and fine point refine * k have the same bits, in the kernels' own
+    fl(origin + fl(step * i)).  (The coarse grid is therefore not grid_of(lo, hi, resolution) to the last bit: its step derives from the fine one.)"""
+    if refine not in (2, 4, 8):
+        raise ValueError("refine: 2, 4 or 8; got %r" % (refine,))
+    dims_c = _resolution3(resolution)
+    dims_f = tuple((n - 1) * refine + 1 for n in dims_c)
+    origin = [float(np.float32(v)) for v in lo]
+    step_f = [float(np.float32((float(h) - float(l)) / (n - 1))) for l, h, n in zip(lo, hi, dims_f)]
+    step_c = [float(np.float32(refine) * np.float32(v)) for v in step_f]
+    return origin, step_c, dims_c, step_f, dims_f
+
+
+def select_cells(coarse_volume, level, dilate=1):
+    """The coarse cells to refine -> bool (nz - 1, ny - 1, nx - 1): those whose eight corners are not all on one side of the level (`inside` is
+    volume > level, as in surface_nets; a NaN corner counts as crossing: what lies there is not known), and the cells within `dilate` cells of
+    one in the 26-neighbourhood."""
+    vol = coarse_volume.detach()
+    nz, ny, nx = vol.shape
+    if min(nz, ny, nx) < 2:
+        return torch.zeros(max(nz - 1, 0), max(ny - 1, 0), max(nx - 1, 0), dtype=torch.bool, device=vol.device)
+    ins, nan = vol > float(level), torch.isnan(vol)
+
+    def cells(t, dx, dy, dz):
+        return t[dz:nz - 1 + dz, dy:ny - 1 + dy, dx:nx - 1 + dx]
+
+    n_in = sum(cells(ins, *c).to(torch.uint8) for c in _CORNERS)
+    sel = (n_in > 0) & (n_in < 8)
+    for c in _CORNERS:
+        sel = sel | cells(nan, *c)
+    dilate = int(dilate)
+    if dilate < 0:
+        raise ValueError("dilate: a cell count >= 0")
+    if dilate:
+        sel = torch.nn.functional.max_pool3d(sel[None, None].to(torch.float32), 2 * dilate + 1, 1, dilate)[0, 0] > 0
+    return sel
+
+
+def _brick_dims(dims_f):
+    return tuple((int(n) + BRICK - 1) // BRICK for n in dims_f)
+
+
+def bricks_for(selected, refine, dims_f):
+    """The bricks of the fine grid that hold any fine point of a selected coarse cell -- cell c's points are refine c .. refine c + refine per
+    axis -> (B,3) int32, columns (bx, by, bz) as the kernel takes them, each brick once, sorted by (bz, by, bx) ascending."""
+    nbx, nby, nbz = _brick_dims(dims_f)
+    cell = selected.nonzero()                                  # (n,3): (cz, cy, cx)
+    first = (cell * refine) // BRICK                           # refine <= BRICK: a cell's points lie in at most two bricks per axis
+    last = (cell * refine + refine) // BRICK
+    keys = []
+    for dz, dy, dx in [(a, b, c) for a in (0, 1) for b in (0, 1) for c in (0, 1)]:
+        bz, by, bx = (last if dz else first)[:, 0], (last if dy else first)[:, 1], (last if dx else first)[:, 2]
+        keys.append((bz * nby + by) * nbx + bx)
+    key = torch.unique(torch.cat(keys))                        # sorted
+    return torch.stack([key % nbx, (key // nbx) % nby, key // (nbx * nby)], 1).to(torch.int32)
+
+
+def sparse_surface_nets(values, bricks, level, origin, step, dims_f):
+    """surface_nets on the part of a fine grid that was evaluated in bricks: values (B,8,8,8) (nnr.ops.density_bricks: [b][lz][ly][lx]),
+    bricks (B,3) integer (bx, by, bz), each brick once, inside the grid; origin, step, dims_f = (nx, ny, nz) the fine grid ->
+    (vertices (V,3) float32, quads (Q,4) int64) on the values' device.  A cell takes part where all of its eight corners lie inside dims_f
+    and in an evaluated brick.  Vertices are ordered by global cell index (z, y, x), quads as surface_nets orders them, and a vertex is
+    computed by the code surface_nets uses (_cell_vertices): where the bricks cover every cell the surface crosses, the result IS
+    surface_nets(dense fine volume), vertex bits and quad rows; in general it is that mesh restricted to the covered cells (a quad needs its
+    four cells covered).  Memory follows B: the brick lookup is one int32 per brick position of the fine grid, the working set 9^3 values
+    per brick; no tensor of the fine grid's size is made."""
+    dev = values.device
+    none = (torch.zeros(0, 3, dtype=torch.float32, device=dev), torch.zeros(0, 4, dtype=torch.int64, device=dev))
+    B = bricks.shape[0]
+    nx, ny, nz = (int(n) for n in dims_f)
+    if B == 0 or min(nx, ny, nz) < 2:
+        return none
+    if tuple(values.shape) != (B, BRICK, BRICK, BRICK):
+        raise ValueError("values: shape %r for %d bricks" % (tuple(values.shape), B))
+    level = float(level)
+    nbx, nby, nbz = _brick_dims(dims_f)
+    bx, by, bz = (bricks[:, c].to(torch.int64) for c in range(3))
+    if int(bx.min()) < 0 or int(by.min()) < 0 or int(bz.min()) < 0 or int(bx.max()) >= nbx or int(by.max()) >= nby or int(bz.max()) >= nbz:
+        raise ValueError("bricks: a brick outside the fine grid's %d x %d x %d bricks" % (nbx, nby, nbz))
+    lookup = torch.full((nbz + 1, nby + 1, nbx + 1), -1, dtype=torch.int32, device=dev)      # (+1: the far neighbours of the last bricks)
+    lookup[bz, by, bx] = torch.arange(B, dtype=torch.int32, device=dev)
+    if int((lookup >= 0).sum()) != B:
+        raise ValueError("bricks: a brick is listed twice")
+
+    # every brick with the first layer of its far neighbours: 9^3 values, and which of them exist (evaluated, and inside the grid)
+    vol = values.detach().to(torch.float64)
+    v9 = torch.zeros(B, BRICK + 1, BRICK + 1, BRICK + 1, dtype=torch.float64, device=dev)
+    has = torch.zeros(B, BRICK + 1, BRICK + 1, BRICK + 1, dtype=torch.bool, device=dev)
+    own, far, one = slice(0, BRICK), slice(BRICK, BRICK + 1), slice(0, 1)
+    for oz, oy, ox in [(a, b, c) for a in (0, 1) for b in (0, 1) for c in (0, 1)]:
+        nb = lookup[bz + oz, by + oy, bx + ox].to(torch.int64)
+        dst = (slice(None), far if oz else own, far if oy else own, far if ox else own)
+        src = (nb.clamp(min=0), one if oz else own, one if oy else own, one if ox else own)
+        v9[dst] = vol[src]
+        has[dst] = (nb >= 0).view(B, 1, 1, 1)
+    k = torch.arange(BRICK + 1, dtype=torch.int64, device=dev)
+    has &= ((BRICK * bz).view(B, 1, 1, 1) + k.view(1, -1, 1, 1) < nz) & ((BRICK * by).view(B, 1, 1, 1) + k.view(1, 1, -1, 1) < ny) & \
+        ((BRICK * bx).view(B, 1, 1, 1) + k.view(1, 1, 1, -1) < nx)
+
+    def cells(t, dx, dy, dz):       # the corner (dx, dy, dz) of every cell of every brick
+        return t[:, dz:BRICK + dz, dy:BRICK + dy, dx:BRICK + dx]
+
+    ins9, nan9 = v9 > level, torch.isnan(v9)
+    n_in = sum(cells(ins9, *c).to(torch.uint8) for c in _CORNERS)
+    ok = cells(has, *_CORNERS[0]) & ~cells(nan9, *_CORNERS[0])
+    for c in _CORNERS[1:]:
+        ok = ok & cells(has, *c) & ~cells(nan9, *c)
+    at = ((n_in > 0) & (n_in < 8) & ok).nonzero()             # (V,4): (b, lz, ly, lx)
+    if at.shape[0] == 0:
+        return none
+    b, lz, ly, lx = at.unbind(1)
+    cz, cy, cx = BRICK * bz[b] + lz, BRICK * by[b] + ly, BRICK * bx[b] + lx
+    key = (cz * (ny - 1) + cy) * (nx - 1) + cx                 # the cell's place in surface_nets' order
+    key, order = key.sort()
+    b, lz, ly, lx, cz, cy, cx = (t[order] for t in (b, lz, ly, lx, cz, cy, cx))
+    V = key.shape[0]
+    val = torch.stack([v9[b, lz + dz, ly + dy, lx + dx] for dx, dy, dz in _CORNERS], 1)      # (V,8)
+    o = torch.tensor([float(v) for v in origin], dtype=torch.float64, device=dev)
+    s = torch.tensor([float(v) for v in step], dtype=torch.float64, device=dev)
+    vertices = _cell_vertices(val, torch.stack([cx, cy, cz], 1), level, o, s)
+
+    # quads: the edge from a cell's corner 0 along `axis` is the grid edge whose (+,+) cell it is; the other three lie one cell back in the
+    # two other axes (surface_nets' rings, seen from that cell).  A cell that is not active has no vertex, so only active cells own quads.
+    side = val > level
+    flip_all = (s[0] * s[1] * s[2]).item() < 0
+    czyx = torch.stack([cz, cy, cx], 1)
+    rings = (((-1, -1, 0), (-1, 0, 0), (0, 0, 0), (0, -1, 0)),          # (dz, dy, dx) from the owning cell; x: y then z
+             ((-1, 0, -1), (0, 0, -1), (0, 0, 0), (-1, 0, 0)),          # y: z then x
+             ((0, -1, -1), (0, -1, 0), (0, 0, 0), (0, 0, -1)))          # z: x then y
+    quads = []
+    for axis, ring in enumerate(rings):
+        others = [c for c in (0, 1, 2) if c != 2 - axis]       # columns of czyx that are not the edge's direction
+        e = ((side[:, 0] != side[:, 1 << axis]) & (czyx[:, others[0]] >= 1) & (czyx[:, others[1]] >= 1)).nonzero().squeeze(1)
+        if e.shape[0] == 0:
+            continue
+        q = []
+        for dz, dy, dx in ring:
+            want = ((cz[e] + dz) * (ny - 1) + (cy[e] + dy)) * (nx - 1) + (cx[e] + dx)
+            pos = torch.searchsorted(key, want).clamp(max=V - 1)
+            q.append(torch.where(key[pos] == want, pos, torch.full_like(pos, -1)))
+        q = torch.stack(q, 1)
+        rev = ~side[e, 0]                                      # the inside end is the far one: the normal points down the axis
+        if flip_all:
+            rev = ~rev
+        q = torch.where(rev.unsqueeze(1), q[:, [0, 3, 2, 1]], q)
+        quads.append(q[(q >= 0).all(1)])
+    quads = torch.cat(quads) if quads else none[1]
+    return vertices, quads
+
+
+def extract_mesh_refined(renderer, lo, hi, resolution, refine, level=None, dilate=1, colour=True, max_bricks=None, chunk=65536, density=None):
+    """The surface {raw density = level} inside [lo, hi] on a grid `refine` (2, 4 or 8) times finer than `resolution`, at a cost that follows
+    the surface: the coarse volume on refined_grid's coarse grid (one launch of the grid kernel) -> select_cells(dilate) -> bricks_for ->
+    nnr.ops.density_bricks (one launch of the brick kernel) -> sparse_surface_nets -> normals and colours as extract_mesh makes them,
+    `chunk` vertices per call (one call's workspace grows with its point count).  The Mesh's origin, step and dims are the fine grid's; it
+    records `refine` and the brick count.
+
+    GUARANTEE AND ITS LIMIT.  The result is the dense fine mesh -- surface_nets of the density on all of the fine grid, which is never made --
+    restricted to what the coarse pass sees: every vertex and quad is one of that mesh's, bit for bit, and every fine cell inside a selected
+    coarse cell is present.  It is never different from the dense fine mesh, only possibly smaller: a component of the surface that crosses
+    no coarse cell within `dilate` cells of a crossing one -- a blob or a gap thinner than a coarse cell that falls between the coarse
+    points -- is absent, at every `dilate`.
+
+    more than max_bricks (None: no bound) selected: ValueError naming the count.  density: (coarse, bricks), two callables
+    coarse(origin, step, dims) -> (nz, ny, nx) and bricks(origin, step, bricks (B,3) int32) -> (B,8,8,8) that stand in for the two kernels;
+    with them the host side runs anywhere (the tests' analytic fields on the CPU); normals and colours are then made only where a renderer
+    is given as well.  Without `density`: GPU only."""
+    net = renderer.model if renderer is not None else None
+    if density is None:
+        w, b = net.weights(), net.biases()
+        if not w[0].is_cuda:
+            raise NotImplementedError("extract_mesh_refined runs only on the GPU (HIP kernels nnr_grid_f16.hip, nnr_bricks_f16.hip) unless "
+                                      "`density` supplies the field")
+        coarse_of = lambda o, s, d: _nnr_ops.density_grid(o, s, d, w, b, hidden=net.hidden_dim)
+        bricks_of = lambda o, s, br: _nnr_ops.density_bricks(o, s, br, w, b, hidden=net.hidden_dim)
+    else:
+        coarse_of, bricks_of = density
+    if level is None:
+        level = level_for(renderer.cfg, net.occ_activation)
+    if int(chunk) < 1:
+        raise ValueError("chunk: at least one vertex per call")
+    origin, step_c, dims_c, step_f, dims_f = refined_grid(lo, hi, resolution, refine)
+    with torch.no_grad():
+        coarse = coarse_of(origin, step_c, dims_c)
+        if tuple(coarse.shape) != tuple(dims_c[::-1]):
+            raise ValueError("coarse volume: shape %r is not the grid's (nz, ny, nx) = %r" % (tuple(coarse.shape), tuple(dims_c[::-1])))
+        selected = select_cells(coarse, level, dilate)
+        bricks = bricks_for(selected, refine, dims_f)
+        n_bricks = int(bricks.shape[0])
+        if max_bricks is not None and n_bricks > max_bricks:
+            raise ValueError("extract_mesh_refined: %d bricks selected (%d coarse cells), more than max_bricks = %d"
+                             % (n_bricks, int(selected.sum()), max_bricks))
+        mesh = Mesh(torch.zeros(0, 3, dtype=torch.float32, device=coarse.device), torch.zeros(0, 4, dtype=torch.int64, device=coarse.device),
+                    level=float(level), origin=tuple(origin), step=tuple(step_f), dims=tuple(dims_f), refine=int(refine), n_bricks=n_bricks)
+        if n_bricks:
+            mesh.vertices, mesh.quads = sparse_surface_nets(bricks_of(origin, step_f, bricks), bricks, level, origin, step_f, dims_f)
+        if net is None or not net.weights()[0].is_cuda:
+            return mesh
+        mesh.normals, mesh.colours = _normals_and_colours(net, mesh.vertices, colour, int(chunk))
+    return mesh
+
+
+def _normals_and_colours(net, vertices, colour, chunk):
+    """extract_mesh's normals and colours, `chunk` vertices per kernel call -> (normals (V,3), colours (V,3) or None)"""
+    w, b = net.weights(), net.biases()
+    normals = torch.zeros_like(vertices)
+    colours = torch.zeros_like(vertices) if colour else None
+    for i in range(0, vertices.shape[0], chunk):
+        v = vertices[i:i + chunk]
+        g = _nnr_ops.density_grad(v, w, b, net.hidden_dim).neg()
+        normals[i:i + chunk] = g / g.norm(2, 1, keepdim=True)
+        if colour:
+            view = torch.nan_to_num(-normals[i:i + chunk])         # (a vanishing gradient: no direction to look along)
+            rgb, _ = _nnr_ops.mlp_points(v, view, w, b, hidden=net.hidden_dim, split2=True)
+            colours[i:i + chunk] = rgb.clamp(0., 1.)
+    return normals, colours
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -54,7 +54,9 @@ LAYER_NAMES = ("layers0.0", "layers0.2", "layers0.4", "layers0.6", "layers1.0", 
 # (2: nnr_pc_error_bwd takes n_dst; round-2 layouts of nnr_aux_cfg and the bf16 plan blob.  3: nnr_step_rays_*; the weight-gradient
 # stage overwrites nnr_param_grads instead of accumulating into it.  4: nnr_ws_plane_layout; the gradient planes of a three-term training workspace
 # are tile-major fp32.  5: nnr_adam_table.flavour / bc2_sqrt -- torch's single-tensor Adam arithmetic beside the fused one; nnr_step_cfg.ref + g_mats: the frame pair of the
-# per-image losses in the fused front end; nnr_aux_terms_*: `aff`, the depth distortion applied in the kernels.  7: nnr_ray_march.  8: nnr_resample; nnr_propose and nnr_density_grid were added under 8: a new function changes none of those)
+# per-image losses in the fused front end; nnr_aux_terms_*: `aff`, the depth distortion applied in the kernels.  7: nnr_ray_march.  8: nnr_resample; nnr_propose and nnr_density_grid were added under 8: a new function changes none of those.
+# Geometry-side entry points added since then are declared in include/nnr_geometry.h, not nnr.h, and listed in GEOMETRY_EXPORTS below: nnr.h's
+# set of functions stays EXPORTS, one to one; nnr_density_bricks is the first, also under 8)
 ABI_VERSION = 8
 EXPORTS = ("nnr_abi_version", "nnr_strerror", "nnr_last_hip_error", "nnr_packed_floats", "nnr_workspace_floats",
            "nnr_plan_bytes", "nnr_plan_counts", "nnr_plan_build", "nnr_pack_weights", "nnr_render_fwd", "nnr_render_bwd", "nnr_ws_plane",
@@ -67,6 +69,8 @@ EXPORTS = ("nnr_abi_version", "nnr_strerror", "nnr_last_hip_error", "nnr_packed_
            "nnr_depth_gather_affine_fwd", "nnr_depth_gather_affine_bwd", "nnr_prof_begin", "nnr_prof_end",
            "nnr_step_rays_fwd", "nnr_step_rays_bwd", "nnr_adam_step", "nnr_uniform_rows", "nnr_ray_march", "nnr_resample", "nnr_propose",
            "nnr_density_grid")
+#: include/nnr_geometry.h
+GEOMETRY_EXPORTS = ("nnr_density_bricks",)
 
 
 class Cfg(C.Structure):
@@ -179,9 +183,10 @@ def load():
     lib.nnr_resample.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.nnr_propose.argtypes = [cfgp, i32] + [vp] * 12
     lib.nnr_density_grid.argtypes = [cfgp, C.POINTER(f32), C.POINTER(f32), C.POINTER(i32), vp, vp, vp]
+    lib.nnr_density_bricks.argtypes = [cfgp, C.POINTER(f32), C.POINTER(f32), vp, i32, vp, vp, vp]
     lib.nnr_prof_begin.argtypes = [i32]
     lib.nnr_prof_end.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-    for n in EXPORTS:
+    for n in EXPORTS + GEOMETRY_EXPORTS:
         if not hasattr(lib, n):
             raise RuntimeError(f"libnnr.so does not export {n}")
     if lib.nnr_abi_version() != ABI_VERSION:

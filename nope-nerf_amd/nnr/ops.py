@@ -392,7 +392,31 @@ def density_grid(origin, step, dims, weights, biases, *, hidden: int) -> torch.T
     return out
 
 
-_P_DOUT4, _P_DPTS = 2, 3      # workspace planes (nnr_layout.h): the per-sample output gradient, the gradient of the sample's point
+def density_bricks(origin, step, bricks: torch.Tensor, weights, biases, *, hidden: int) -> torch.Tensor:
+    """The raw density in a list of 8 x 8 x 8 bricks of the grid (origin, step) in one launch of nnr_density_bricks (include/nnr_geometry.h):
+    bricks (B,3) int32 on the weights' device, (bx, by, bz) per brick, non-negative -> (B, 8, 8, 8) fp32, [b][lz][ly][lx]: the grid point
+    (8 bx + lx, 8 by + ly, 8 bz + lz).  Every voxel is density_grid's value at the same grid point, bit for bit.  Bricks may repeat and come in
+    any order; the grid has no dims here, a brick that reaches past its last point is evaluated all the same.  Always in the two-term fp16
+    products (split2_cfg), with the cached pack, as density_grid.  Not differentiable.  No host synchronisation."""
+    weights, biases = list(weights), list(biases)
+    _require_gpu(weights[0])
+    if bricks.dtype != torch.int32 or bricks.dim() != 2 or bricks.shape[1] != 3 or bricks.device != weights[0].device:
+        raise ValueError("density_bricks: bricks must be a (B,3) int32 tensor on the weights' device; got %r %r on %s"
+                         % (tuple(bricks.shape), bricks.dtype, bricks.device))
+    B = bricks.shape[0]
+    if B < 1 or 512 * B > 2 ** 31 - 1:
+        raise ValueError("density_bricks: %d bricks: at least one and at most %d (2^31 - 1 voxels) in one call" % (B, (2 ** 31 - 1) // 512))
+    cfg = split2_cfg(512 * B, 1, hidden)
+    packed = _packed_for(cfg, weights, biases)
+    bricks = bricks.contiguous()
+    out = torch.empty(B, 8, 8, 8, dtype=torch.float32, device=weights[0].device)
+    o3 = (C.c_float * 3)(*[float(v) for v in origin])
+    s3 = (C.c_float * 3)(*[float(v) for v in step])
+    L.check(L.load().nnr_density_bricks(C.byref(cfg), o3, s3, L.ptr(bricks), B, L.ptr(packed), L.ptr(out), L.stream()), "nnr_density_bricks")
+    return out
+
+
+_P_DOUT4, _P_DPTS = 2, 3     # workspace planes (nnr_layout.h): the per-sample output gradient, the gradient of the sample's point
 
 
 def density_grad(points: torch.Tensor, weights, biases, hidden: int) -> torch.Tensor:

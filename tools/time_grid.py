@@ -119,14 +119,15 @@ def main():
     summarise_trace(args.out)
 
 
-def summarise_trace(out):
-    """rocprofv3's files under OUT/trace -> OUT/kernel_stats.csv (copied) and OUT/kernel_trace_summary.json; OUT/trace is removed"""
-    trace = os.path.join(out, "trace")
+def summarise_trace(out, prefix=""):
+    """rocprofv3's files under OUT/<prefix>trace -> OUT/<prefix>kernel_stats.csv (copied) and OUT/<prefix>kernel_trace_summary.json;
+    OUT/<prefix>trace is removed (prefix: tools/time_bricks.py keeps its files beside this tool's)"""
+    trace = os.path.join(out, prefix + "trace")
     stats = glob.glob(os.path.join(trace, "**", "*kernel_stats.csv"), recursive=True)
     traces = glob.glob(os.path.join(trace, "**", "*kernel_trace.csv"), recursive=True)
     if len(stats) != 1 or len(traces) != 1:
-        sys.exit("time_grid: expected one kernel_stats.csv and one kernel_trace.csv under %s, found %r and %r" % (trace, stats, traces))
-    shutil.copyfile(stats[0], os.path.join(out, "kernel_stats.csv"))
+        sys.exit("expected one kernel_stats.csv and one kernel_trace.csv under %s, found %r and %r" % (trace, stats, traces))
+    shutil.copyfile(stats[0], os.path.join(out, prefix + "kernel_stats.csv"))
     ns = {}
     with open(traces[0], newline="") as f:
         for row in csv.DictReader(f):
@@ -135,7 +136,7 @@ def summarise_trace(out):
             ns.setdefault((row["Kernel_Name"], threads), []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
     summary = [dict(kernel=k, grid_threads=g, calls=len(v), ns_min=min(v), ns_median=statistics.median(v), ns_max=max(v), ns_total=sum(v))
                for (k, g), v in sorted(ns.items(), key=lambda kv: -sum(kv[1]))]
-    with open(os.path.join(out, "kernel_trace_summary.json"), "w") as f:
+    with open(os.path.join(out, prefix + "kernel_trace_summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     shutil.rmtree(trace)
     for line in summary[:12]:
