@@ -11,20 +11,21 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_DIR = os.path.join(HERE, "build")
 LIB = os.path.join(os.path.dirname(HERE), "nnr", "libnnr.so")
 # (source, defines): the two fp32 MLP kernels are compiled one template instantiation per translation unit -- each is minutes of hipcc
-# time (straight-line code of ~8 000 MFMAs), in one unit the forward alone took 8.5 minutes; the longest unit first
-SOURCES = [("nnr_wgrad.hip", ()), ("nnr_wgrad.hip", ("NNR_WGRAD_F16_TU=1",)), ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=256",)),
+# time (straight-line code of ~8 000 MFMAs), in one unit the forward alone took 8.5 minutes.  The longest units first: the two D = 256
+# three-term forwards take some 25 minutes each where the next longest takes 13, so a full build lasts as long as they do from their start
+SOURCES = [("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MODE=2")), ("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=0", "NNR_FWD_MODE=2")),
+           ("nnr_wgrad.hip", ()), ("nnr_wgrad.hip", ("NNR_WGRAD_F16_TU=1",)), ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=256",)),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=0")),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=128",)),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_march_f16.hip", ()), ("nnr_propose_f16.hip", ()), ("nnr_grid_f16.hip", ()), ("nnr_bricks_f16.hip", ()),
-           ("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MODE=2")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_MODE=2")),
-           ("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=0", "NNR_FWD_MODE=2")),
+           ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_MODE=2")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1", "NNR_FWD_MODE=2")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=128", "NNR_DGRAD_MODE=2")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0", "NNR_FWD_MODE=2")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1")), ("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=0")),
            ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256",)), ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=128",)),
-           ("nnr_mlp_fwd_bf16.hip", ()), ("nnr_mlp_dgrad_bf16.hip", ()), ("nnr_mlp_fwd.hip", ()), ("nnr_mlp_dgrad.hip", ()),
-           ("nnr_api.cpp", ()), ("nnr_wgrad_plan.cpp", ()), ("nnr_pack.hip", ()), ("nnr_wgrad_bf16.hip", ()), ("nnr_composite.hip", ()), ("nnr_resample.hip", ()),
+           ("nnr_mlp_fwd_bf16.hip", ()), ("nnr_mlp_dgrad_bf16.hip", ()), ("nnr_mlp_fwd.hip", ()), ("nnr_mlp_dgrad.hip", ()), ("nnr_depth_f16.hip", ()),
+           ("nnr_api.cpp", ()), ("nnr_wgrad_plan.cpp", ()), ("nnr_fusion_api.cpp", ()), ("nnr_tsdf.hip", ()), ("nnr_pack.hip", ()), ("nnr_wgrad_bf16.hip", ()), ("nnr_composite.hip", ()), ("nnr_resample.hip", ()),
            ("nnr_camera.hip", ()), ("nnr_pointcloud.hip", ()), ("nnr_aux.hip", ()), ("nnr_randperm.hip", ()), ("nnr_optim.hip", ())]
 
 
@@ -32,11 +33,14 @@ def _obj_name(src, defines):
     tag = "".join("_" + d.split("=")[0].lower().replace("nnr_", "") + d.split("=")[1] for d in defines)
     return os.path.splitext(src)[0] + tag + ".o"
 SPLIT2_ONLY = ["nnr_split2.h", "nnr_trunk_f16.h", "nnr_trunk_f16.inc"]      # included by the fp16-term kernels (the `_f16` units: forward, input gradient, march, proposal, grid, bricks) only: touching them does not rebuild the rest (minutes per unit)
-DENSITY_ONLY = ["nnr_density_setup_f16.inc", "nnr_density_pass_f16.inc"]      # the density-only pass of the march, proposal, grid and bricks kernels: touching it rebuilds those four units, not the forward and input-gradient `_f16` units
-DENSITY_UNITS = ("nnr_march_f16.hip", "nnr_propose_f16.hip", "nnr_grid_f16.hip", "nnr_bricks_f16.hip")
+DENSITY_ONLY = ["nnr_density_setup_f16.inc", "nnr_density_pass_f16.inc"]      # the density-only pass of the march, proposal, grid, bricks and depth kernels: touching it rebuilds those five units, not the forward and input-gradient `_f16` units
+DENSITY_UNITS = ("nnr_march_f16.hip", "nnr_propose_f16.hip", "nnr_grid_f16.hip", "nnr_bricks_f16.hip", "nnr_depth_f16.hip")
 ROW_ONLY = ["nnr_resample_row.h"]      # the row code of hierarchical sampling: nnr_resample.hip and nnr_propose_f16.hip
 FWD_ONLY = ["nnr_mlp_fwd_common.h"]      # included by nnr_mlp_fwd.hip and, through nnr_trunk_f16.h, by the `_f16` units
 GEOMETRY_ONLY = [os.path.join("..", "..", "include", "nnr_geometry.h")]      # the geometry-side entry points' header: nnr_api.cpp alone
+FUSION_ONLY = ["nnr_fusion_kernels.h"]      # the depth-fusion side's argument blocks and launchers: nnr_depth_f16.hip, nnr_tsdf.hip and their host unit nnr_fusion_api.cpp
+FUSION_UNITS = ("nnr_depth_f16.hip", "nnr_tsdf.hip", "nnr_fusion_api.cpp")
+FUSION_API_ONLY = [os.path.join("..", "..", "include", "nnr_fusion.h")]      # the depth-fusion entry points' header: nnr_fusion_api.cpp alone
 PLAN_ONLY = ["nnr_wgrad_plan.h"]      # the host planners' header (no kernel includes it): nnr_api.cpp and nnr_wgrad_plan.cpp
 HEADERS = ["nnr_layout.h", "nnr_device.h", "nnr_kernels.h", "nnr_mlp_bf16.h", "nnr_split.h", os.path.join("..", "..", "include", "nnr.h")]
 # -pragma-unroll-threshold: the MLP kernels are straight-line code by construction (every `#pragma unroll` loop must unroll fully, or
@@ -54,7 +58,8 @@ SCRATCH_LIMIT = {"18mlp_fwd_f16_kernelI": 0, "18mlp_fwd_f16_kernelILi256ELb0E": 
                  "20mlp_dgrad_f16_kernelI": 0, "14mlp_fwd_kernelI": 0, "14mlp_fwd_kernelILi256ELb1ELi2E": 48, "16mlp_dgrad_kernelI": 0, "12wgrad_kernelI": 0, "14wgrad_b_kernelE": 0,
                  "19mlp_fwd_bf16_kernelI": 48, "19mlp_fwd_bf16_kernelILi256ELb1E": 16, "19mlp_fwd_bf16_kernelILi128ELb1E": 16,
                  "21mlp_dgrad_bf16_kernelI": 64, "20composite_fwd_kernelE": 0, "20composite_bwd_kernelE": 0,
-                 "16march_f16_kernelI": 0, "19march_finish_kernel": 0, "15resample_kernelE": 0, "18propose_f16_kernelI": 0, "15grid_f16_kernelI": 0, "17bricks_f16_kernelI": 0}
+                 "16march_f16_kernelI": 0, "19march_finish_kernel": 0, "15resample_kernelE": 0, "18propose_f16_kernelI": 0, "15grid_f16_kernelI": 0, "17bricks_f16_kernelI": 0,
+                 "16depth_f16_kernelI": 0, "21tsdf_integrate_kernelE": 0}
 
 
 def check_resources(remarks, what):
@@ -121,6 +126,10 @@ def own_headers(src):
         own = own + PLAN_ONLY
     if src == "nnr_api.cpp":
         own = own + GEOMETRY_ONLY
+    if src in FUSION_UNITS:
+        own = own + FUSION_ONLY
+    if src == "nnr_fusion_api.cpp":
+        own = own + FUSION_API_ONLY
     return own
 
 

@@ -24,13 +24,6 @@ namespace {
 
 thread_local int g_last_hip = 0;
 
-// the one launch-result path: what a launcher (or any HIP call) returned -> the entry point's return code
-int launched(hipError_t e) {
-    if (e == hipSuccess) return NNR_OK;
-    g_last_hip = (int)e;
-    return NNR_E_HIP;
-}
-
 bool aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }      // n a power of two; null passes
 
 int check_cfg(const nnr_cfg* c) {
@@ -89,6 +82,16 @@ CompositeArgs composite_args(const nnr_cfg* cfg, float* ws) {
 }
 
 }  // namespace
+
+// the one launch-result path: what a launcher (or any HIP call) returned -> the entry point's return code.  Not file-local: the host unit of
+// include/nnr_fusion.h (nnr_fusion_api.cpp) reports through it too, so that nnr_last_hip_error speaks for every entry point.
+namespace nnr {
+int launched(hipError_t e) {
+    if (e == hipSuccess) return NNR_OK;
+    g_last_hip = (int)e;
+    return NNR_E_HIP;
+}
+}  // namespace nnr
 
 // ---- in-step kernel timing -------------------------------------------------------------------------------------------------
 // bench.py switches this on for its timed steps: every launch of a main MLP kernel is bracketed by two HIP events recorded on the

@@ -7,6 +7,9 @@
     extract_mesh_refined   a coarse volume -> the 8^3 bricks of a 2, 4 or 8 times finer grid around the coarse cells the surface crosses
                      (refined_grid, select_cells, bricks_for; nnr.ops.density_bricks) -> surface nets on those bricks alone
                      (sparse_surface_nets) -> normals and colours in chunks: the dense fine mesh restricted to what the coarse pass sees
+    extract_mesh_tsdf      the rendered depth maps of known cameras (render_depth_maps: nnr.ops.render_depth) fused into a truncated signed
+                     distance volume in bricks (nnr.ops.tsdf_integrate; projection_rows, tsdf_volume, tsdf_select_cells) -> surface nets of its
+                     zero set, dense or refined: no density level, surface only where some camera saw one
     write_ply / read_ply
 
 Grid conventions, shared with the kernel: a volume is (nz, ny, nx), x fastest; grid point (ix, iy, iz) sits at origin + step * (ix, iy, iz)
@@ -479,6 +482,213 @@ def _normals_and_colours(net, vertices, colour, chunk):
             rgb, _ = _nnr_ops.mlp_points(v, view, w, b, hidden=net.hidden_dim, split2=True)
             colours[i:i + chunk] = rgb.clamp(0., 1.)
     return normals, colours
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the TSDF mesh: rendered depth maps fused into a truncated signed distance volume
+# ----------------------------------------------------------------------------------------------------------------------
+@dataclass
+class Cameras:
+    """The views a TSDF is fused from: one intrinsic matrix, one world matrix (world -> camera) per view, the image size."""
+    camera_mat: torch.Tensor                     # (4,4) or (1,4,4)
+    world_mats: torch.Tensor                     # (n,4,4)
+    size: tuple                                  # (H, W)
+    scale_mat: Optional[torch.Tensor] = None     # (4,4) or (1,4,4); None: the identity
+
+
+def _mat44(m, n=None):
+    m = torch.as_tensor(m).detach().to('cpu', torch.float64)
+    m = m.reshape(-1, 4, 4)
+    if n is not None and m.shape[0] == 1:
+        m = m.expand(n, 4, 4)
+    return m
+
+
+def projection_rows(camera_mat, world_mat, scale_mat=None):
+    """Rows 0..2 of K . world_mat . scale_mat per camera -> (n,12) fp32 on the CPU, row-major: what transform_to_camera_space followed by
+    project_to_cam (model/common.py) apply to a world point, as the one matrix nnr.ops.tsdf_integrate takes.  world_mat (n,4,4) or (4,4);
+    camera_mat and scale_mat (4,4), (1,4,4) or one per camera; scale_mat None: the identity.  The product is formed in float64 and rounded
+    to fp32 once."""
+    W = _mat44(world_mat)
+    n = W.shape[0]
+    K = _mat44(camera_mat, n)
+    S = _mat44(scale_mat, n) if scale_mat is not None else torch.eye(4, dtype=torch.float64).expand(n, 4, 4)
+    if K.shape[0] != n or S.shape[0] != n:
+        raise ValueError("projection_rows: %d camera and %d scale matrices for %d world matrices" % (K.shape[0], S.shape[0], n))
+    return (K @ W @ S)[:, :3, :].reshape(n, 12).to(torch.float32).contiguous()
+
+
+def render_depth_maps(renderer, camera_mat, world_mats, size, min_acc=0.5, chunk=1 << 18, scale_mat=None):
+    """The z-depth maps of renderer.model seen from the cameras (camera_mat, world_mats[i]) -> (n, H, W) fp32 on the model's device: what
+    nope_nerf(eval_=True) reports as depth, without its colour.  Rays come from nnr.camera.ray_setup on arange_pixels((H, W)), the samples
+    from the renderer's own z tables without noise; the rendered distance is divided by ray_norm under rendering.normalise_ray.
+    Pixels whose accumulated weight is below min_acc (the phong renderer's tau) become +inf: the ray saw free space; NaN stays NaN.
+    With C = num_points - outside_steps <= 256 samples the depth comes from the fused depth kernel (nnr.ops.render_depth: the density alone,
+    8 bytes per ray), otherwise from nnr.render_rays' forward-only depth and its per-sample alphas.  chunk: rays per launch.
+    sample_option 'ndc': NotImplementedError -- NDC depths are not world depths.  GPU only."""
+    import nnr
+    from nnr import camera as _camera
+    from .common import arange_pixels
+    cfg, net = renderer.cfg, renderer.model
+    if cfg['sample_option'] == 'ndc':
+        raise NotImplementedError("render_depth_maps: rendering.sample_option 'ndc' samples in NDC space, whose depths are not world depths")
+    if cfg['sample_option'] != 'uniform':
+        raise ValueError('unknown sample_option %r' % (cfg['sample_option'],))
+    w, b = net.weights(), net.biases()
+    dev = w[0].device
+    if not w[0].is_cuda:
+        raise NotImplementedError("render_depth_maps runs only on the GPU (HIP kernels nnr_depth_f16.hip / the render kernels)")
+    H, W = (int(v) for v in size)
+    if int(chunk) < 1:
+        raise ValueError("chunk: at least one ray per launch")
+    f32 = dict(dtype=torch.float32, device=dev)
+    world_mats = torch.as_tensor(world_mats).detach().to(**f32).reshape(-1, 4, 4)
+    n = world_mats.shape[0]
+    K = torch.as_tensor(camera_mat).detach().to(**f32).reshape(-1, 4, 4)[:1]
+    S = torch.as_tensor(scale_mat).detach().to(**f32).reshape(-1, 4, 4)[:1] if scale_mat is not None else torch.eye(4, **f32)[None]
+    n_samples = int(cfg['num_points']) - int(cfg['outside_steps'])
+    normalise, use_dir = bool(cfg['normalise_ray']), bool(cfg['use_ray_dir'])
+    dist_alpha, relu_sigma = bool(cfg['dist_alpha']), net.occ_activation != 'softplus'
+    pixels = arange_pixels((H, W), device=dev)[1]                                          # (1, H W, 2), row-major
+    out = torch.empty(n, H * W, **f32)
+    with torch.no_grad():
+        z_lo, z_hi = renderer._z_tables(n_samples, renderer.depth_range[0], renderer.depth_range[1], False, dev)
+        for i in range(n):
+            origin, ray, view, ray_norm, _, _ = _camera.ray_setup(pixels, None, K, world_mats[i:i + 1], S, normalise, use_dir)
+            for r0 in range(0, H * W, int(chunk)):
+                sl = slice(r0, min(r0 + int(chunk), H * W))
+                if n_samples <= 256:
+                    da = _nnr_ops.render_depth(origin[sl], ray[sl], z_lo, z_hi, None, w, b, hidden=net.hidden_dim, dist_alpha=dist_alpha,
+                                               relu_sigma=relu_sigma)
+                    depth, acc = da[:, 0], da[:, 1]
+                else:
+                    _, depth, alpha, _ = nnr.render_rays(origin[sl], ray[sl], view[sl], z_lo, z_hi, None, w, b, hidden=net.hidden_dim,
+                                                         dist_alpha=dist_alpha, white_bg=False, relu_sigma=relu_sigma, samples=True)
+                    T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), (1. - alpha[:, :-1]) + 1e-6], 1), 1)
+                    acc = (alpha * T).sum(1)
+                if normalise:
+                    depth = depth / ray_norm[sl]
+                out[i, sl] = torch.where(acc < float(min_acc), torch.full_like(depth, float('inf')), depth)
+    return out.view(n, H, W)
+
+
+def tsdf_volume(sum, weight):
+    """sum / weight of the accumulators nnr.ops.tsdf_integrate fills, NaN where the weight is 0: no camera observed the voxel"""
+    return torch.where(weight > 0, sum / weight, torch.full_like(sum, float('nan')))
+
+
+def tsdf_select_cells(volume, dilate=1):
+    """The coarse cells of a TSDF volume to refine -> bool (nz - 1, ny - 1, nx - 1): those whose FINITE corners are not all on one side of 0
+    (`inside` is volume > 0, as in surface_nets), and the cells within `dilate` cells of one in the 26-neighbourhood.  A NaN corner does not
+    count as a crossing here -- the one deliberate difference from select_cells: unobserved space is most of a TSDF volume, and refining it
+    all would make the sparse path dense."""
+    vol = volume.detach()
+    nz, ny, nx = vol.shape
+    if min(nz, ny, nx) < 2:
+        return torch.zeros(max(nz - 1, 0), max(ny - 1, 0), max(nx - 1, 0), dtype=torch.bool, device=vol.device)
+    ins, out = vol > 0., vol <= 0.                                 # (a NaN is neither)
+
+    def cells(t, dx, dy, dz):
+        return t[dz:nz - 1 + dz, dy:ny - 1 + dy, dx:nx - 1 + dx]
+
+    any_in, any_out = cells(ins, *_CORNERS[0]), cells(out, *_CORNERS[0])
+    for c in _CORNERS[1:]:
+        any_in, any_out = any_in | cells(ins, *c), any_out | cells(out, *c)
+    sel = any_in & any_out
+    dilate = int(dilate)
+    if dilate < 0:
+        raise ValueError("dilate: a cell count >= 0")
+    if dilate:
+        sel = torch.nn.functional.max_pool3d(sel[None, None].to(torch.float32), 2 * dilate + 1, 1, dilate)[0, 0] > 0
+    return sel
+
+
+def _all_bricks(dims, device):
+    """every brick of the grid, (B,3) int32 (bx, by, bz), sorted by (bz, by, bx) ascending as bricks_for sorts"""
+    nbx, nby, nbz = _brick_dims(dims)
+    key = torch.arange(nbx * nby * nbz, dtype=torch.int64, device=device)
+    return torch.stack([key % nbx, (key // nbx) % nby, key // (nbx * nby)], 1).to(torch.int32)
+
+
+def _dense_from_bricks(values, dims):
+    """(B,8,8,8) of _all_bricks(dims) -> the (nz, ny, nx) volume, cropped to the grid"""
+    nbx, nby, nbz = _brick_dims(dims)
+    nx, ny, nz = dims
+    return values.view(nbz, nby, nbx, BRICK, BRICK, BRICK).permute(0, 3, 1, 4, 2, 5).reshape(BRICK * nbz, BRICK * nby, BRICK * nbx)[:nz, :ny, :nx]
+
+
+def extract_mesh_tsdf(renderer, cameras, lo, hi, resolution, refine=None, trunc_voxels=3, dilate=1, colour=True, integrate=None,
+                      depth_maps=None, min_acc=0.5, chunk=65536, max_bricks=None):
+    """The zero set of the truncated signed distance volume fused from the model's rendered depth maps of `cameras` (a Cameras) inside the box
+    [lo, hi], as a Mesh at level 0 (Curless-Levoy with weight 1 per observation): what the model was trained on -- the rendered depth of
+    its learned cameras -- and not a level of the raw density.  `inside` (positive) is behind the surfaces the cameras saw.
+
+      refine None   the dense path: every brick of grid_of(lo, hi, resolution) is integrated (nnr.ops.tsdf_integrate), the accumulators
+                    become sum / weight, NaN where unobserved (tsdf_volume), scattered into the (nz, ny, nx) volume -> surface_nets(., 0).
+      refine 2|4|8  the refined path: that dense volume on refined_grid's coarse grid -> tsdf_select_cells(dilate) -> bricks_for ->
+                    the same depth maps integrated on those fine bricks alone -> sparse_surface_nets(., 0).  As for extract_mesh_refined the
+                    result is the dense fine mesh restricted to what the coarse pass sees.
+      trunc_voxels  the truncation distance in steps of the grid that is being integrated (the largest |step| of its three): the coarse
+                    volume is truncated at trunc_voxels coarse steps, the fine bricks at trunc_voxels fine steps.
+      depth_maps    (n,H,W) z-depth maps on the integrator's device where the caller has them, or a callable () -> such maps (a timer's
+                    hook); None: render_depth_maps(renderer, ...) with min_acc.
+      integrate     a callable (origin, step, bricks, cams, depth, trunc, sum, weight) that stands in for nnr.ops.tsdf_integrate (the CPU
+                    tests' reference integrator, a timer's hook); with it and depth_maps the host side runs anywhere, normals and colours
+                    are then made only where a renderer on the GPU is given as well.
+    Normals and colours are the density field's at the vertices, as the other two extractors make them (_normals_and_colours)."""
+    net = renderer.model if renderer is not None else None
+    on_gpu = net is not None and net.weights()[0].is_cuda
+    if (integrate is None or depth_maps is None) and not on_gpu:
+        raise NotImplementedError("extract_mesh_tsdf runs only on the GPU (HIP kernels nnr_depth_f16.hip, nnr_tsdf.hip) unless `integrate` and "
+                                  "`depth_maps` supply the depth maps and their fusion")
+    if not trunc_voxels > 0:
+        raise ValueError("trunc_voxels: a positive number of grid steps")
+    if integrate is None:
+        integrate = lambda o, s, br, cm, dp, tr, sm, wt: _nnr_ops.tsdf_integrate(o, s, br, cm, dp, tr, sm, wt)
+    with torch.no_grad():
+        if depth_maps is None:
+            depth = render_depth_maps(renderer, cameras.camera_mat, cameras.world_mats, cameras.size, min_acc=min_acc, scale_mat=cameras.scale_mat)
+        else:
+            depth = depth_maps() if callable(depth_maps) else depth_maps
+        depth = depth.detach().to(torch.float32).contiguous()
+        dev = depth.device
+        cams = projection_rows(cameras.camera_mat, cameras.world_mats, cameras.scale_mat).to(dev)
+        if depth.dim() != 3 or depth.shape[0] != cams.shape[0]:
+            raise ValueError("depth maps: shape %r for %d cameras" % (tuple(depth.shape), cams.shape[0]))
+
+        def fuse(origin, step, bricks):
+            acc = torch.zeros(2, bricks.shape[0], BRICK, BRICK, BRICK, dtype=torch.float32, device=dev)
+            trunc = float(np.float32(trunc_voxels) * np.float32(max(abs(v) for v in step)))
+            integrate(origin, step, bricks, cams, depth, trunc, acc[0], acc[1])
+            return tsdf_volume(acc[0], acc[1])
+
+        if refine is None:
+            origin, step, dims = grid_of(lo, hi, resolution)
+            bricks = _all_bricks(dims, dev)
+            vol = _dense_from_bricks(fuse(origin, step, bricks), dims)
+            vertices, quads = surface_nets(vol, 0., origin, step)
+            mesh = Mesh(vertices, quads, level=0., origin=tuple(origin), step=tuple(step), dims=tuple(dims), n_bricks=int(bricks.shape[0]))
+        else:
+            origin, step_c, dims_c, step, dims = refined_grid(lo, hi, resolution, refine)
+            coarse = _dense_from_bricks(fuse(origin, step_c, _all_bricks(dims_c, dev)), dims_c)
+            selected = tsdf_select_cells(coarse, dilate)
+            bricks = bricks_for(selected, refine, dims)
+            n_bricks = int(bricks.shape[0])
+            if max_bricks is not None and n_bricks > max_bricks:
+                raise ValueError("extract_mesh_tsdf: %d bricks selected (%d coarse cells), more than max_bricks = %d"
+                                 % (n_bricks, int(selected.sum()), max_bricks))
+            mesh = Mesh(torch.zeros(0, 3, dtype=torch.float32, device=dev), torch.zeros(0, 4, dtype=torch.int64, device=dev), level=0.,
+                        origin=tuple(origin), step=tuple(step), dims=tuple(dims), refine=int(refine), n_bricks=n_bricks)
+            if n_bricks:
+                mesh.vertices, mesh.quads = sparse_surface_nets(fuse(origin, step, bricks), bricks, 0., origin, step, dims)
+        if not on_gpu or not mesh.vertices.is_cuda:
+            return mesh
+        if mesh.vertices.shape[0] == 0:
+            mesh.normals = torch.zeros_like(mesh.vertices)
+            mesh.colours = torch.zeros_like(mesh.vertices) if colour else None
+            return mesh
+        mesh.normals, mesh.colours = _normals_and_colours(net, mesh.vertices, colour, int(chunk))
+    return mesh
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -71,6 +71,8 @@ EXPORTS = ("nnr_abi_version", "nnr_strerror", "nnr_last_hip_error", "nnr_packed_
            "nnr_density_grid")
 #: include/nnr_geometry.h
 GEOMETRY_EXPORTS = ("nnr_density_bricks",)
+#: include/nnr_fusion.h: the depth-fusion side of the geometry export, also under ABI 8
+FUSION_EXPORTS = ("nnr_render_depth", "nnr_tsdf_integrate")
 
 
 class Cfg(C.Structure):
@@ -184,9 +186,11 @@ def load():
     lib.nnr_propose.argtypes = [cfgp, i32] + [vp] * 12
     lib.nnr_density_grid.argtypes = [cfgp, C.POINTER(f32), C.POINTER(f32), C.POINTER(i32), vp, vp, vp]
     lib.nnr_density_bricks.argtypes = [cfgp, C.POINTER(f32), C.POINTER(f32), vp, i32, vp, vp, vp]
+    lib.nnr_render_depth.argtypes = [cfgp] + [vp] * 10
+    lib.nnr_tsdf_integrate.argtypes = [C.POINTER(f32), C.POINTER(f32), vp, i32, vp, i32, vp, i32, i32, f32, f32, vp, vp, vp]
     lib.nnr_prof_begin.argtypes = [i32]
     lib.nnr_prof_end.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-    for n in EXPORTS + GEOMETRY_EXPORTS:
+    for n in EXPORTS + GEOMETRY_EXPORTS + FUSION_EXPORTS:
         if not hasattr(lib, n):
             raise RuntimeError(f"libnnr.so does not export {n}")
     if lib.nnr_abi_version() != ABI_VERSION:

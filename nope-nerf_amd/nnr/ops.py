@@ -416,6 +416,61 @@ def density_bricks(origin, step, bricks: torch.Tensor, weights, biases, *, hidde
     return out
 
 
+def render_depth(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor, jitter: Optional[torch.Tensor], weights, biases, *,
+                 hidden: int, dist_alpha: bool, relu_sigma: bool, debug: bool = False):
+    """The rendered depth of rays from the density alone in one launch of nnr_render_depth (include/nnr_fusion.h): the inputs of a render_rays
+    call without the view direction -> (R,2) fp32, (depth, acc) per ray: depth = sum w_j z_j and acc = sum w_j over the compositor's weights.
+    No colour branch, nothing per sample written to HBM.  Always in the two-term fp16 products (split2_cfg), with the cached pack, as propose.
+    (NaN, NaN) for a ray with a NaN sample.  debug: (out, raw (R,C), z (R,C)), the samples' raw densities and depths.  1 <= C <= 256.
+    Not differentiable.  No host synchronisation."""
+    _require_gpu(pts_o)
+    R, Cn = pts_o.shape[0], z_lo.shape[0]
+    dev = pts_o.device
+    cfg = split2_cfg(R, Cn, hidden, dist_alpha=dist_alpha, relu_sigma=relu_sigma)
+    pts_o, pts_d = pts_o.detach().contiguous().float(), pts_d.detach().contiguous().float()
+    z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
+    jit = jitter.detach().contiguous().float().view(R, Cn) if jitter is not None else None
+    packed = _packed_for(cfg, list(weights), list(biases))
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = torch.empty(R, 2, **f32)
+    raw, zv = (torch.empty(R, Cn, **f32), torch.empty(R, Cn, **f32)) if debug else (None, None)
+    L.check(L.load().nnr_render_depth(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), L.ptr(packed), L.ptr(out),
+                                      L.ptr(raw), L.ptr(zv), L.stream()), "nnr_render_depth")
+    return (out, raw, zv) if debug else out
+
+
+def tsdf_integrate(origin, step, bricks: torch.Tensor, cams: torch.Tensor, depth: torch.Tensor, trunc: float, sum: torch.Tensor,
+                   weight: torch.Tensor, z_min: float = 0.):
+    """Integrate depth maps into the truncated signed distance accumulators of a list of 8 x 8 x 8 bricks of the grid (origin, step), IN PLACE,
+    in one launch of nnr_tsdf_integrate (include/nnr_fusion.h): bricks (B,3) int32 as density_bricks takes them, cams (n,12) fp32 (rows 0..2 of
+    K . world_mat . scale_mat: model.geometry.projection_rows), depth (n,H,W) fp32 z-depth (NaN, 0 and negative: unobserved; +inf: free space),
+    sum and weight (B,8,8,8) fp32, all on one GPU.  Per voxel and camera, in index order: sum += max((q_z - d) / trunc, -1), weight += 1 where
+    the voxel projects into the image in front of z_min and lies no further than trunc behind the depth d of its pixel.  Cameras may come in
+    chunks over several calls: the result is the one-call result bit for bit.  Returns (sum, weight).  No host synchronisation."""
+    _require_gpu(sum)
+    dev = sum.device
+    if bricks.dtype != torch.int32 or bricks.dim() != 2 or bricks.shape[1] != 3 or bricks.device != dev:
+        raise ValueError("tsdf_integrate: bricks must be a (B,3) int32 tensor on the accumulators' device; got %r %r on %s"
+                         % (tuple(bricks.shape), bricks.dtype, bricks.device))
+    B = bricks.shape[0]
+    if B < 1 or 512 * B > 2 ** 31 - 1:
+        raise ValueError("tsdf_integrate: %d bricks: at least one and at most %d (2^31 - 1 voxels) in one call" % (B, (2 ** 31 - 1) // 512))
+    if cams.dim() != 2 or cams.shape[1] != 12 or depth.dim() != 3 or depth.shape[0] != cams.shape[0] or cams.shape[0] < 1:
+        raise ValueError("tsdf_integrate: cams (n,12) and depth (n,H,W), n >= 1; got %r and %r" % (tuple(cams.shape), tuple(depth.shape)))
+    for name, t in (("cams", cams), ("depth", depth), ("sum", sum), ("weight", weight)):
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError("tsdf_integrate: %s must be a contiguous fp32 tensor on the accumulators' device" % name)
+    if tuple(sum.shape) != (B, 8, 8, 8) or tuple(weight.shape) != (B, 8, 8, 8):
+        raise ValueError("tsdf_integrate: sum and weight must be (%d, 8, 8, 8); got %r and %r" % (B, tuple(sum.shape), tuple(weight.shape)))
+    n, H, W = depth.shape
+    bricks = bricks.contiguous()
+    o3 = (C.c_float * 3)(*[float(v) for v in origin])
+    s3 = (C.c_float * 3)(*[float(v) for v in step])
+    L.check(L.load().nnr_tsdf_integrate(o3, s3, L.ptr(bricks), B, L.ptr(cams), n, L.ptr(depth), H, W, float(trunc), float(z_min), L.ptr(sum),
+                                        L.ptr(weight), L.stream()), "nnr_tsdf_integrate")
+    return sum, weight
+
+
 _P_DOUT4, _P_DPTS = 2, 3     # workspace planes (nnr_layout.h): the per-sample output gradient, the gradient of the sample's point
 
 

@@ -6,6 +6,11 @@ one.  GPU only (the render path has no CPU fallback).
 
     python tools/scene_writer.py /tmp/scenes --frames 16 --size 120 160
     python tools/train_scene.py /tmp/scenes synthetic --epochs 200 [--style tanks|llff] [--host-loader] [--out result.json]
+                                [--checkpoint-dir DIR]
+
+--checkpoint-dir: after the last epoch write model.pt, model_pose.pt (and model_focal.pt where a focal is learnt) there through
+CheckpointIO, in the layout train.py writes and tools/extract_mesh.py loads (save_checkpoints), next to config.yaml: the run's whole
+configuration with training.out_dir = DIR, which that tool takes as its config (with --default pointing at no file).
 
 Reported per run: PSNR of the training rays (from l2_mean, as train.py:283-285 does), ATE / RPE of the learned poses against the
 scene's ground truth after sim(3) alignment (train.py:270-281), loop throughput in steps/s and rays/s.  One host sync per epoch
@@ -70,6 +75,16 @@ def build(cfg, device, n_views):
     return trainer, pose, dist
 
 
+def save_checkpoints(out_dir, nope, pose, focal=None, **scalars):
+    """model.pt, model_pose.pt and, with a focal net, model_focal.pt in out_dir: one CheckpointIO file per module group, each registered as
+    'model', as train.py writes them (tools/extract_mesh.py: load_pose_table reads the pose table back)."""
+    import model as mdl
+    mdl.CheckpointIO(out_dir, model=nope).save("model.pt", **scalars)
+    mdl.CheckpointIO(out_dir, model=pose).save("model_pose.pt", **scalars)
+    if focal is not None:
+        mdl.CheckpointIO(out_dir, model=focal).save("model_focal.pt", **scalars)
+
+
 def pose_errors(pose_net, gt_poses, n_views):
     from utils_poses.align_traj import align_ate_c2b_use_a2b
     from utils_poses.comp_ate import compute_ATE, compute_rpe
@@ -123,7 +138,7 @@ def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_poi
             "seconds_per_frame": dt / max(1, len(rows))}
 
 
-def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=None, eval_epochs=0, eval_dir=None, **cfg_kw):
+def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=None, eval_epochs=0, eval_dir=None, checkpoint_dir=None, **cfg_kw):
     """-> dict with the per-epoch PSNR / pose-error curve and the loop throughput (+ novel-view scores with eval_epochs > 0)."""
     import dataloading as dl
     from model.common import mse2psnr
@@ -158,6 +173,14 @@ def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=No
                 print(json.dumps(curve[-1]), flush=True)
     trainer.flush_nan_check()        # the step's NaN check is one step late by design: look at the last one too
     n_rays = cfg["training"]["n_training_points"]
+    if checkpoint_dir and parallel.is_writer():
+        save_checkpoints(checkpoint_dir, trainer.model, pose, epoch_it=epochs - 1, it=it)
+        import yaml
+        full = json.loads(json.dumps(cfg))      # plain containers
+        full["dataloading"]["path"] = os.path.abspath(path)
+        full["training"]["out_dir"] = os.path.abspath(checkpoint_dir)
+        with open(os.path.join(checkpoint_dir, "config.yaml"), "w") as fh:
+            yaml.safe_dump(full, fh)
     novel = None
     if eval_epochs > 0:
         import tempfile
@@ -192,8 +215,9 @@ def main():
     ap.add_argument("--eval-epochs", type=int, default=0, help="test-time pose optimisation epochs before scoring the held-out views")
     ap.add_argument("--eval-dir", default=None, help="where the rendered held-out frames go (default: a temporary directory)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--checkpoint-dir", default=None, help="write model.pt, model_pose.pt and config.yaml here after the last epoch (tools/extract_mesh.py takes DIR/config.yaml)")
     a = ap.parse_args()
-    res = run(a.path, a.scene, style=a.style, epochs=a.epochs, log_every=a.log_every, eval_epochs=a.eval_epochs, eval_dir=a.eval_dir, n_rays=a.rays, n_samples=a.samples,
+    res = run(a.path, a.scene, style=a.style, epochs=a.epochs, log_every=a.log_every, eval_epochs=a.eval_epochs, eval_dir=a.eval_dir, checkpoint_dir=a.checkpoint_dir, n_rays=a.rays, n_samples=a.samples,
               hidden=a.hidden, resident=not a.host_loader, aux=not a.no_aux, resize_factor=a.factor, workers=a.workers,
               mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine, proposal=a.proposal)
     print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
