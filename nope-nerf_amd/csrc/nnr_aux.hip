@@ -434,7 +434,7 @@ __global__ __launch_bounds__(64 * kPcLanes) void aux_pc_search_kernel(AuxArgs a,
     int best_i = 0x7fffffff;
     auto consider = [&](float d2, int idx) __attribute__((always_inline)) {
         if (d2 <= thr && d2 < __builtin_inff()) {
-            const float sq = __fsqrt_rn(d2);
+            const float sq = __builtin_sqrtf(d2);      // correctly rounded, as in nnr_pointcloud.hip: the two searches agree bit for bit
             if (sq < best_s || (sq == best_s && idx < best_i)) {
                 best_s = sq;
                 best_i = idx;
@@ -659,7 +659,7 @@ __global__ __launch_bounds__(64 * kPcTileWaves) void aux_pc_search_tile_kernel(A
     int best_i = 0x7fffffff;
     auto consider = [&](float d2, int idx) __attribute__((always_inline)) {
         if (d2 <= thr && d2 < __builtin_inff()) {
-            const float sq = __fsqrt_rn(d2);
+            const float sq = __builtin_sqrtf(d2);      // correctly rounded, as in nnr_pointcloud.hip: the two searches agree bit for bit
             if (sq < best_s || (sq == best_s && idx < best_i)) {
                 best_s = sq;
                 best_i = idx;

@@ -10,6 +10,9 @@
 // Parity: the reference takes argmin over sqrt(dx^2 + dy^2 + dz^2) as torch evaluates it -- the sum of squares as the fma
 // chain fma(dz,dz, fma(dy,dy, dx*dx)) (checked bit-for-bit against torch.linalg.norm on the host) -- and returns the FIRST
 // index of the minimum.  The kernel forms the same fp32 value and orders candidates by (sqrt bits, index).
+// The square root is __builtin_sqrtf, the correctly rounded one (v_sqrt_f32 and a one-ulp fix-up).  HIP's __fsqrt_rn is, despite its name,
+// the bare v_sqrt_f32 (1 ulp): on d2 that fp32 holds exactly it returned a neighbour of the reference's root for some values, and with
+// it another winner where two d2 share one correctly rounded root (tests/test_gpu_pc_nearest.py).  The sqrt is off the steady-state path.
 #include "nnr_device.h"
 #include "nnr_kernels.h"
 #include <cstdlib>
@@ -78,7 +81,7 @@ __global__ __launch_bounds__(kPcBlock) void pc_nearest_kernel(const float* __res
                 for (int u = 0; u < kPcPer; ++u) {
                     const float v = d2[k][u >> 1][u & 1];
                     if (v < best_d2[u >> 1][u & 1]) {
-                        const float sq = __fsqrt_rn(v);
+                        const float sq = __builtin_sqrtf(v);      // correctly rounded (see the top of the file)
                         if (sq < best_s[u]) { best_s[u] = sq; best_i[u] = i0 + k; }   // equal sqrt: the earlier index stays
                         best_d2[u >> 1][u & 1] = v;
                     }
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(kPcBlock) void pc_nearest_one_kernel(const float* _
     for (int u = 0; u < SRC; ++u) { best_s[u] = __builtin_inff(); thr[u] = __builtin_inff(); best_i[u] = 0x7fffffff; }
     auto consider = [&](int u, float v, int idx) __attribute__((always_inline)) {
         if (v <= thr[u] && v < __builtin_inff()) {      // (padding points and infinite distances never match)
-            const float sq = __fsqrt_rn(v);
+            const float sq = __builtin_sqrtf(v);      // correctly rounded (see the top of the file)
             if (sq < best_s[u] || (sq == best_s[u] && idx < best_i[u])) {
                 best_s[u] = sq;
                 best_i[u] = idx;
