@@ -17,7 +17,7 @@ SOURCES = [("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MOD
            ("nnr_wgrad.hip", ()), ("nnr_wgrad.hip", ("NNR_WGRAD_F16_TU=1",)), ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=256",)),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=0")),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=128",)),
-           ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_march_f16.hip", ()), ("nnr_propose_f16.hip", ()), ("nnr_grid_f16.hip", ()), ("nnr_bricks_f16.hip", ()),
+           ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_sparse_f16.hip", ()), ("nnr_march_f16.hip", ()), ("nnr_propose_f16.hip", ()), ("nnr_grid_f16.hip", ()), ("nnr_bricks_f16.hip", ()),
            ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_MODE=2")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1", "NNR_FWD_MODE=2")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=128", "NNR_DGRAD_MODE=2")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0", "NNR_FWD_MODE=2")),
@@ -25,14 +25,14 @@ SOURCES = [("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MOD
            ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256",)), ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=128",)),
            ("nnr_mlp_fwd_bf16.hip", ()), ("nnr_mlp_dgrad_bf16.hip", ()), ("nnr_mlp_fwd.hip", ()), ("nnr_mlp_dgrad.hip", ()), ("nnr_depth_f16.hip", ()),
-           ("nnr_api.cpp", ()), ("nnr_wgrad_plan.cpp", ()), ("nnr_fusion_api.cpp", ()), ("nnr_tsdf.hip", ()), ("nnr_pack.hip", ()), ("nnr_wgrad_bf16.hip", ()), ("nnr_composite.hip", ()), ("nnr_resample.hip", ()),
+           ("nnr_api.cpp", ()), ("nnr_wgrad_plan.cpp", ()), ("nnr_fusion_api.cpp", ()), ("nnr_sparse_api.cpp", ()), ("nnr_tsdf.hip", ()), ("nnr_pack.hip", ()), ("nnr_wgrad_bf16.hip", ()), ("nnr_composite.hip", ()), ("nnr_resample.hip", ()),
            ("nnr_camera.hip", ()), ("nnr_pointcloud.hip", ()), ("nnr_aux.hip", ()), ("nnr_randperm.hip", ()), ("nnr_optim.hip", ())]
 
 
 def _obj_name(src, defines):
     tag = "".join("_" + d.split("=")[0].lower().replace("nnr_", "") + d.split("=")[1] for d in defines)
     return os.path.splitext(src)[0] + tag + ".o"
-SPLIT2_ONLY = ["nnr_split2.h", "nnr_trunk_f16.h", "nnr_trunk_f16.inc"]      # included by the fp16-term kernels (the `_f16` units: forward, input gradient, march, proposal, grid, bricks) only: touching them does not rebuild the rest (minutes per unit)
+SPLIT2_ONLY = ["nnr_split2.h", "nnr_trunk_f16.h", "nnr_trunk_f16.inc"]      # included by the fp16-term kernels (the `_f16` units: forward, input gradient, march, proposal, grid, bricks, depth, sparse) only: touching them does not rebuild the rest (minutes per unit)
 DENSITY_ONLY = ["nnr_density_setup_f16.inc", "nnr_density_pass_f16.inc"]      # the density-only pass of the march, proposal, grid, bricks and depth kernels: touching it rebuilds those five units, not the forward and input-gradient `_f16` units
 DENSITY_UNITS = ("nnr_march_f16.hip", "nnr_propose_f16.hip", "nnr_grid_f16.hip", "nnr_bricks_f16.hip", "nnr_depth_f16.hip")
 ROW_ONLY = ["nnr_resample_row.h"]      # the row code of hierarchical sampling: nnr_resample.hip and nnr_propose_f16.hip
@@ -41,6 +41,9 @@ GEOMETRY_ONLY = [os.path.join("..", "..", "include", "nnr_geometry.h")]      # t
 FUSION_ONLY = ["nnr_fusion_kernels.h"]      # the depth-fusion side's argument blocks and launchers: nnr_depth_f16.hip, nnr_tsdf.hip and their host unit nnr_fusion_api.cpp
 FUSION_UNITS = ("nnr_depth_f16.hip", "nnr_tsdf.hip", "nnr_fusion_api.cpp")
 FUSION_API_ONLY = [os.path.join("..", "..", "include", "nnr_fusion.h")]      # the depth-fusion entry points' header: nnr_fusion_api.cpp alone
+SPARSE_ONLY = ["nnr_sparse_kernels.h"]      # the sparse inference render's argument block and launcher: nnr_sparse_f16.hip and its host unit nnr_sparse_api.cpp
+SPARSE_UNITS = ("nnr_sparse_f16.hip", "nnr_sparse_api.cpp")
+SPARSE_API_ONLY = [os.path.join("..", "..", "include", "nnr_sparse.h")]      # the sparse render's entry point's header: nnr_sparse_api.cpp alone
 PLAN_ONLY = ["nnr_wgrad_plan.h"]      # the host planners' header (no kernel includes it): nnr_api.cpp and nnr_wgrad_plan.cpp
 HEADERS = ["nnr_layout.h", "nnr_device.h", "nnr_kernels.h", "nnr_mlp_bf16.h", "nnr_split.h", os.path.join("..", "..", "include", "nnr.h")]
 # -pragma-unroll-threshold: the MLP kernels are straight-line code by construction (every `#pragma unroll` loop must unroll fully, or
@@ -59,7 +62,8 @@ SCRATCH_LIMIT = {"18mlp_fwd_f16_kernelI": 0, "18mlp_fwd_f16_kernelILi256ELb0E": 
                  "19mlp_fwd_bf16_kernelI": 48, "19mlp_fwd_bf16_kernelILi256ELb1E": 16, "19mlp_fwd_bf16_kernelILi128ELb1E": 16,
                  "21mlp_dgrad_bf16_kernelI": 64, "20composite_fwd_kernelE": 0, "20composite_bwd_kernelE": 0,
                  "16march_f16_kernelI": 0, "19march_finish_kernel": 0, "15resample_kernelE": 0, "18propose_f16_kernelI": 0, "15grid_f16_kernelI": 0, "17bricks_f16_kernelI": 0,
-                 "16depth_f16_kernelI": 0, "21tsdf_integrate_kernelE": 0}
+                 "16depth_f16_kernelI": 0, "21tsdf_integrate_kernelE": 0,
+                 "17sparse_f16_kernelI": 48}      # (the inference forward's passes and composite carry: its allowance)
 
 
 def check_resources(remarks, what):
@@ -130,6 +134,10 @@ def own_headers(src):
         own = own + FUSION_ONLY
     if src == "nnr_fusion_api.cpp":
         own = own + FUSION_API_ONLY
+    if src in SPARSE_UNITS:
+        own = own + SPARSE_ONLY
+    if src == "nnr_sparse_api.cpp":
+        own = own + SPARSE_API_ONLY
     return own
 
 

@@ -1,0 +1,53 @@
+// nnr_sparse_api.cpp -- the extern "C" entry point of include/nnr_sparse.h (the sparse inference render): argument checking and marshalling
+// into the kernel's argument struct (nnr_sparse_kernels.h).  A host unit of its own, as nnr_fusion_api.cpp is.  Every error return is
+// decided before any device work -- no pointer is dereferenced here except the host arrays of the grid -- and the call is asynchronous on
+// the caller's stream.  No state: the last HIP error is nnr_api.cpp's (launched).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/nnr_sparse.h"
+#include "nnr_sparse_kernels.h"
+
+using namespace nnr;
+
+namespace {
+
+bool aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }      // n a power of two; null passes
+
+}  // namespace
+
+extern "C" {
+
+int nnr_render_sparse(const nnr_cfg* cfg, const float* pts_o, const float* pts_d, const float* view_d, const float* z_lo, const float* z_hi,
+                      const float* jitter, const float grid_lo[3], const float grid_inv_step[3], const int32_t grid_dims[3],
+                      const uint32_t* bits, const float* packed, float* out, int32_t* opt_count, int32_t* opt_cell, float* opt_out4,
+                      void* stream) {
+    if (!cfg || cfg->n_rays < 1 || cfg->n_samples < 1) return NNR_E_BADCFG;
+    if (!pts_o || !pts_d || !view_d || !z_lo || !z_hi || !grid_lo || !grid_inv_step || !grid_dims || !bits || !packed || !out)
+        return NNR_E_BADCFG;      // (jitter and the opt_* may be null)
+    for (int c = 0; c < 3; ++c) {
+        if (grid_dims[c] < 1) return NNR_E_BADCFG;
+        if (!std::isfinite(grid_lo[c]) || !std::isfinite(grid_inv_step[c]) || !(grid_inv_step[c] > 0.f)) return NNR_E_BADCFG;
+    }
+    if (cfg->n_samples > 256 || (cfg->hidden != 128 && cfg->hidden != 256)) return NNR_E_UNSUPPORTED;
+    if ((cfg->flags & (NNR_F_BF16 | NNR_F_SPLIT3 | NNR_F_SPLIT2)) != (NNR_F_SPLIT3 | NNR_F_SPLIT2) || (cfg->flags & NNR_F_TRAIN)) return NNR_E_UNSUPPORTED;
+    const int64_t wx = ((int64_t)grid_dims[0] + 31) / 32;
+    const int64_t rows = (int64_t)grid_dims[2] * grid_dims[1];      // < 2^62
+    if (rows > INT32_MAX || rows * wx > INT32_MAX || rows * grid_dims[0] > INT32_MAX) return NNR_E_UNSUPPORTED;
+    if (!aligned(packed, 16)) return NNR_E_ALIGN;
+    for (const void* p : {(const void*)pts_o, (const void*)pts_d, (const void*)view_d, (const void*)z_lo, (const void*)z_hi, (const void*)jitter,
+                          (const void*)bits, (const void*)out, (const void*)opt_count, (const void*)opt_cell, (const void*)opt_out4})
+        if (!aligned(p, 4)) return NNR_E_ALIGN;
+    SparseArgs a{};
+    a.pts_o = pts_o; a.pts_d = pts_d; a.view_d = view_d; a.z_lo = z_lo; a.z_hi = z_hi; a.jitter = jitter; a.bits = bits; a.packed = packed;
+    a.out = out; a.opt_count = opt_count; a.opt_cell = opt_cell; a.opt_out4 = opt_out4;
+    for (int c = 0; c < 3; ++c) { a.lo[c] = grid_lo[c]; a.inv_step[c] = grid_inv_step[c]; a.n[c] = grid_dims[c]; }
+    a.wx = (int)wx;
+    a.R = cfg->n_rays; a.C = cfg->n_samples;
+    a.flags = cfg->flags & (NNR_F_RELU_SIGMA | NNR_F_DIST_ALPHA | NNR_F_WHITE_BG);
+    return launched(launch_render_sparse(cfg->hidden, a, (hipStream_t)stream));
+}
+
+}  // extern "C"

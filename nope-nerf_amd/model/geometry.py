@@ -11,6 +11,8 @@
                      distance volume in bricks (nnr.ops.tsdf_integrate; projection_rows, tsdf_volume, tsdf_select_cells) -> surface nets of its
                      zero set, dense or refined: no density level, surface only where some camera saw one
     write_ply / read_ply
+    occupancy_bits / OccupancyGrid / occupancy_grid / level_for_alpha   the volume as a bitfield of cells that may hold matter, for the sparse
+                     inference render (nnr.ops.render_sparse)
 
 Grid conventions, shared with the kernel: a volume is (nz, ny, nx), x fastest; grid point (ix, iy, iz) sits at origin + step * (ix, iy, iz)
 (fp32: the product rounded, then the sum).  There is no CPU volume path: the density comes from the HIP kernel or not at all."""
@@ -765,3 +767,91 @@ def read_ply(path):
     return dict(vertices=cols(('x', 'y', 'z'), np.float32), normals=cols(('nx', 'ny', 'nz'), np.float32),
                 colours=cols(('red', 'green', 'blue'), np.uint8), faces=faces['i'].astype(np.int64))
 
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the occupancy grid of the sparse inference render
+# ----------------------------------------------------------------------------------------------------------------------
+def level_for_alpha(alpha_min, delta, occ_activation):
+    """The raw density whose compositor alpha at sample spacing `delta` is alpha_min: the inverse of the kernels' sample_alpha.
+
+        sigma = -log(1 - alpha_min) / delta          rendering.dist_alpha: alpha = 1 - exp(-sigma delta)
+        sigma = -log(1 - alpha_min)                  without it (delta None): alpha = 1 - exp(-sigma)
+        raw = log(exp(sigma) - 1)                    occ_activation 'softplus': sigma = softplus(raw)
+        raw = sigma                                  otherwise: sigma = relu(raw)
+
+    alpha is non-decreasing in raw and in delta: a sample with raw < level at a spacing <= delta has alpha < alpha_min.  0 < alpha_min < 1."""
+    alpha_min = float(alpha_min)
+    if not 0. < alpha_min < 1.:
+        raise ValueError("alpha_min = %r: an alpha strictly between 0 and 1" % alpha_min)
+    sigma = -math.log1p(-alpha_min)
+    if delta is not None:
+        if not float(delta) > 0.:
+            raise ValueError("delta = %r: a positive sample spacing (None without rendering.dist_alpha)" % (delta,))
+        sigma = sigma / float(delta)
+    if occ_activation == 'softplus':
+        return math.log(math.expm1(sigma))
+    return sigma
+
+
+def occupancy_bits(volume, level, dilate=1):
+    """The cells of a density volume that may hold matter, as the bitfield nnr_render_sparse reads (include/nnr_sparse.h): volume (nz, ny, nx)
+    grid points -> int32 (nz - 1, ny - 1, w_x), w_x = ceil((nx - 1) / 32), on the volume's device.  Cell (i_x, i_y, i_z) spans the grid points
+    i to i + 1 on every axis; it is occupied iff any of its 8 corners has raw >= level or is NaN (what lies there is not known), or if it lies
+    within `dilate` cells of such a cell in the max norm.  Cell i_x is bit i_x & 31 of word [i_z][i_y][i_x >> 5]; the words are uint32 bit
+    patterns held as int32 (bit 31 is the sign).  Plain torch, CPU or GPU tensors."""
+    vol = volume.detach()
+    nz, ny, nx = vol.shape
+    if min(nz, ny, nx) < 2:
+        raise ValueError("occupancy_bits: a volume of at least 2 grid points per axis; got %r" % ((nz, ny, nx),))
+    dilate = int(dilate)
+    if dilate < 0:
+        raise ValueError("dilate: a cell count >= 0")
+    hot = (vol >= float(level)) | torch.isnan(vol)
+    occ = torch.zeros(nz - 1, ny - 1, nx - 1, dtype=torch.bool, device=vol.device)
+    for dx, dy, dz in _CORNERS:
+        occ = occ | hot[dz:nz - 1 + dz, dy:ny - 1 + dy, dx:nx - 1 + dx]
+    if dilate:
+        occ = torch.nn.functional.max_pool3d(occ[None, None].to(torch.float32), 2 * dilate + 1, 1, dilate)[0, 0] > 0
+    cx = nx - 1
+    wx = (cx + 31) // 32
+    padded = torch.zeros(nz - 1, ny - 1, wx * 32, dtype=torch.int64, device=vol.device)
+    padded[..., :cx] = occ.to(torch.int64)
+    words = (padded.view(nz - 1, ny - 1, wx, 32) << torch.arange(32, dtype=torch.int64, device=vol.device)).sum(-1)
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words)      # the uint32 pattern as int32
+    return words.to(torch.int32).contiguous()
+
+
+@dataclass
+class OccupancyGrid:
+    """What nnr.ops.render_sparse takes as `grid`: cell i_c of axis c spans [lo_c + i_c / inv_step_c, + 1 / inv_step_c); dims = (n_x, n_y, n_z)
+    cells; bits as occupancy_bits packs them.  `occupied`: the share of cells whose bit is set (a 0-dim tensor on the bits' device)."""
+    lo: tuple
+    inv_step: tuple
+    dims: tuple
+    bits: torch.Tensor
+    occupied: Optional[torch.Tensor] = None
+
+
+def occupancy_grid(renderer, lo, hi, resolution, level, dilate=1, slab=None):
+    """The occupancy grid of renderer.model over the box [lo, hi] with `resolution` CELLS per axis (one int or (n_x, n_y, n_z)): the raw density
+    on the resolution + 1 grid points per axis (density_volume: the fused grid kernel, GPU only), thresholded at `level` (occupancy_bits).
+    The kernel finds a sample's cell as (p - lo) * inv_step with inv_step = fl(1 / step) of the volume's fp32 step: a cell border may sit
+    a few ulp from the grid point it stands for, which a dilation of one cell covers many times over."""
+    cells = (int(resolution),) * 3 if isinstance(resolution, int) else tuple(int(v) for v in resolution)
+    if len(cells) != 3 or min(cells) < 1:
+        raise ValueError("resolution: one int or (n_x, n_y, n_z), at least one cell per axis; got %r" % (resolution,))
+    points = tuple(n + 1 for n in cells)
+    origin, step, _ = grid_of(lo, hi, points)
+    if not all(s > 0. for s in step):
+        raise ValueError("occupancy_grid: hi must exceed lo on every axis; got %r, %r" % (lo, hi))
+    bits = occupancy_bits(density_volume(renderer, lo, hi, points, slab=slab), level, dilate)
+    inv = tuple(float(np.float32(1.) / np.float32(s)) for s in step)
+    return OccupancyGrid(tuple(origin), inv, cells, bits, occupied_share(bits, cells))
+
+
+def occupied_share(bits, dims):
+    """The share of a grid's cells whose bit is set -> 0-dim fp32 tensor on the bits' device (no host synchronisation)."""
+    b = bits.to(torch.int64) & 0xFFFFFFFF
+    ones = sum(((b >> k) & 1) for k in range(32)).sum()
+    return ones.to(torch.float32) / float(int(dims[0]) * int(dims[1]) * int(dims[2]))

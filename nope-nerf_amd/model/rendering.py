@@ -21,6 +21,8 @@ The phong geometry visualiser (`phong_renderer`, `ray_marching`, `secant`; refer
 its secant steps in one HIP kernel (nnr_march_f16.hip via nnr.ops.ray_march), the normals through the training kernels
 (nnr.ops.density_grad), always in the two-term fp16 products.  On CPU tensors they raise NotImplementedError.
 """
+import logging
+
 import torch
 import torch.nn as nn
 
@@ -221,8 +223,17 @@ class Renderer(nn.Module):
                 z_lo, z_hi = self._unit_tables(n_samples + n_fine, device)      # z = 0 + (1 - 0) * jitter: the kernels take the depths as given
                 jitter = _nnr_ops.resample(alpha_c, z_c, xi, n_fine)
         lazy_samples = not torch.is_grad_enabled()   # evaluation / visualisation: per-sample outputs only if somebody reads them
-        rgb, dist_pred, alpha, z_val = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(),
-                                                       samples=not lazy_samples, **kw)
+        grid = self._occupancy_grid(pixels, z_lo, kw) if cfg.get('occupancy', None) is not None else None
+        if grid is not None:
+            # rendering.occupancy: the sparse inference render (nnr_sparse_f16.hip), the samples in known-empty cells skipped; alpha / z_vals,
+            # if somebody reads them, still come from the dense pass below
+            rgb, dist_pred, _ = _nnr_ops.render_sparse(pts_o, pts_d, view, z_lo, z_hi, jitter, grid, net.weights(), net.biases(),
+                                                       hidden=kw['hidden'], dist_alpha=kw['dist_alpha'], white_bg=kw['white_bg'],
+                                                       relu_sigma=kw['relu_sigma'])
+            alpha = z_val = None
+        else:
+            rgb, dist_pred, alpha, z_val = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(),
+                                                           samples=not lazy_samples, **kw)
 
         diff_norm = None
         if cfg['normal_loss'] and not eval_:
@@ -242,6 +253,60 @@ class Renderer(nn.Module):
             'mask': object_mask,
             'ndc': cfg['sample_option'] == 'ndc',
         })
+
+    # ------------------------------------------------------------------------------------------------ sparse inference render
+    def _occupancy_grid(self, pixels, z_lo, kw):
+        """rendering.occupancy: {resolution: N, alpha_min: A, dilate: 1, bounds: [lo, hi]} -> the occupancy grid of the sparse inference render
+        (model.geometry.occupancy_grid), or None where the dense path has to run (one logged line per reason).  N cells per axis over
+        `bounds` (two scalars or two triples; default: the cube of rendering.radius under sample_option 'uniform'; required under 'ndc', where
+        the grid lives in the MLP's input space); a cell is empty where the raw density at its 8 corners stays below the level whose alpha at
+        the coarse sample spacing is alpha_min (geometry.level_for_alpha; required: no default), `dilate` cells (default 1) around the others
+        kept.  Built on first use and kept exactly as long as the packed weights it was built from are valid: the same parameter objects
+        and no optimiser step since (nnr.ops.ParamsStamp)."""
+        from . import geometry
+        cfg = self.cfg
+        occ = cfg['occupancy']
+        n_render = int(z_lo.shape[0])
+        why = None
+        if torch.is_grad_enabled():
+            why = "gradients are enabled (the sparse render is forward-only)"
+        elif not pixels.is_cuda:
+            why = "the tensors are not on the GPU"
+        elif kw['bf16']:
+            why = "rendering.mfma_dtype is bf16 (the sparse kernel has two-term fp16 products only)"
+        elif n_render > 256:
+            why = "%d samples per ray (the sparse kernel takes at most 256)" % n_render
+        if why is not None:
+            seen = self.__dict__.setdefault('_occupancy_said', set())
+            if why not in seen:
+                seen.add(why)
+                logging.getLogger(__name__).info("rendering.occupancy: dense render, %s", why)
+            return None
+        if 'alpha_min' not in occ or 'resolution' not in occ:
+            raise ValueError("rendering.occupancy needs `resolution` and `alpha_min` (no defaults: DESIGN.md section 12)")
+        bounds = occ.get('bounds', None)
+        if bounds is None:
+            if cfg['sample_option'] != 'uniform':
+                raise ValueError("rendering.occupancy.bounds must be given under sample_option %r (default only under 'uniform': the cube of "
+                                 "rendering.radius)" % (cfg['sample_option'],))
+            bounds = [-float(cfg['radius']), float(cfg['radius'])]
+        lo, hi = ([float(b)] * 3 if not isinstance(b, (list, tuple)) else [float(v) for v in b] for b in bounds)
+        net = self.model
+        w, b = net.weights(), net.biases()
+        hit = self.__dict__.get('_occupancy_hit', None)
+        key = (tuple(lo), tuple(hi), repr(occ.get('resolution')), float(occ['alpha_min']), int(occ.get('dilate', 1)), kw['dist_alpha'], kw['relu_sigma'])
+        if hit is not None and hit[0] == key and hit[1].matches(w, b):
+            return hit[2]
+        n_coarse = cfg['num_points'] - cfg['outside_steps']
+        near, far = (0., 1.) if cfg['sample_option'] == 'ndc' else (float(self.depth_range[0]), float(self.depth_range[1]))
+        delta = (far - near) / max(n_coarse - 1, 1) if kw['dist_alpha'] else None      # the coarse spacing: fine samples lie closer
+        level = geometry.level_for_alpha(occ['alpha_min'], delta, 'relu' if kw['relu_sigma'] else 'softplus')
+        res = occ['resolution']
+        grid = geometry.occupancy_grid(self, lo, hi, int(res) if not isinstance(res, (list, tuple)) else tuple(res), level, int(occ.get('dilate', 1)))
+        stamp = _nnr_ops.ParamsStamp(w, b)      # (after the build: density_volume packs the weights if need be)
+        self.__dict__['_occupancy_hit'] = (key, stamp, grid)
+        self.occupancy_builds = getattr(self, 'occupancy_builds', 0) + 1
+        return grid
 
     def _normal_consistency(self, origin, ray, d_gt, mask, it):
         """|n(x) - n(x + eps)| at the surface points x the mono depth puts on the valid rays, n = normalised -d(sigma)/dx

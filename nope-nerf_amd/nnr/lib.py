@@ -73,6 +73,8 @@ EXPORTS = ("nnr_abi_version", "nnr_strerror", "nnr_last_hip_error", "nnr_packed_
 GEOMETRY_EXPORTS = ("nnr_density_bricks",)
 #: include/nnr_fusion.h: the depth-fusion side of the geometry export, also under ABI 8
 FUSION_EXPORTS = ("nnr_render_depth", "nnr_tsdf_integrate")
+#: include/nnr_sparse.h: the sparse inference render, also under ABI 8
+SPARSE_EXPORTS = ("nnr_render_sparse",)
 
 
 class Cfg(C.Structure):
@@ -188,9 +190,10 @@ def load():
     lib.nnr_density_bricks.argtypes = [cfgp, C.POINTER(f32), C.POINTER(f32), vp, i32, vp, vp, vp]
     lib.nnr_render_depth.argtypes = [cfgp] + [vp] * 10
     lib.nnr_tsdf_integrate.argtypes = [C.POINTER(f32), C.POINTER(f32), vp, i32, vp, i32, vp, i32, i32, f32, f32, vp, vp, vp]
+    lib.nnr_render_sparse.argtypes = [cfgp] + [vp] * 6 + [C.POINTER(f32), C.POINTER(f32), C.POINTER(i32)] + [vp] * 7
     lib.nnr_prof_begin.argtypes = [i32]
     lib.nnr_prof_end.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-    for n in EXPORTS + GEOMETRY_EXPORTS + FUSION_EXPORTS:
+    for n in EXPORTS + GEOMETRY_EXPORTS + FUSION_EXPORTS + SPARSE_EXPORTS:
         if not hasattr(lib, n):
             raise RuntimeError(f"libnnr.so does not export {n}")
     if lib.nnr_abi_version() != ABI_VERSION:

@@ -439,6 +439,58 @@ def render_depth(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z
     return (out, raw, zv) if debug else out
 
 
+def render_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor,
+                  jitter: Optional[torch.Tensor], grid, weights, biases, *, hidden: int, dist_alpha: bool, white_bg: bool, relu_sigma: bool,
+                  debug: bool = False):
+    """A forward-only render that evaluates the MLP only on the samples an occupancy grid does not call empty, in one launch of
+    nnr_render_sparse (include/nnr_sparse.h): the inputs of a render_rays call plus `grid` -- an object with lo, inv_step (three floats each),
+    dims = (n_x, n_y, n_z) cells and bits, the (n_z, n_y, ceil(n_x / 32)) int32 words on the rays' device (model.geometry.OccupancyGrid) ->
+    rgb (R,3), dist (R) = sum w z, acc (R) = sum w.  A sample outside the grid, or in a cell whose bit is set, is evaluated and composited with
+    the alpha it has in the dense render; a sample in a cell whose bit is clear is skipped.  Always in the two-term fp16 products
+    (split2_cfg), with the cached pack, as propose.  debug: (rgb, dist, acc, count (R) int32, cell (R,C) int32, out4 (R,C,4) with NaN rows for
+    the culled samples).  Any R, 1 <= C <= 256.  Not differentiable.  No host synchronisation."""
+    _require_gpu(pts_o)
+    R, Cn = pts_o.shape[0], z_lo.shape[0]
+    dev = pts_o.device
+    flags = L.NNR_F_SPLIT3 | L.NNR_F_SPLIT2 | (L.NNR_F_DIST_ALPHA if dist_alpha else 0) | (L.NNR_F_RELU_SIGMA if relu_sigma else 0) | \
+        (L.NNR_F_WHITE_BG if white_bg else 0)
+    cfg = L.Cfg(int(R), int(Cn), int(hidden), flags)
+    pts_o, pts_d, view_d = (t.detach().contiguous().float() for t in (pts_o, pts_d, view_d))
+    z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
+    jit = jitter.detach().contiguous().float().view(R, Cn) if jitter is not None else None
+    nx, ny, nz = (int(n) for n in grid.dims)
+    bits = grid.bits
+    if bits.dtype != torch.int32 or bits.device != dev or not bits.is_contiguous() or bits.numel() != nz * ny * ((nx + 31) // 32):
+        raise ValueError("render_sparse: grid.bits must be a contiguous int32 tensor of %d words on the rays' device; got %r %r on %s"
+                         % (nz * ny * ((nx + 31) // 32), tuple(bits.shape), bits.dtype, bits.device))
+    packed = _packed_for(cfg, list(weights), list(biases))
+    out = torch.empty(R, 5, dtype=torch.float32, device=dev)
+    count = cell = out4 = None
+    if debug:
+        count = torch.empty(R, dtype=torch.int32, device=dev)
+        cell = torch.empty(R, Cn, dtype=torch.int32, device=dev)
+        out4 = torch.full((R, Cn, 4), float("nan"), dtype=torch.float32, device=dev)
+    lo3 = (C.c_float * 3)(*[float(v) for v in grid.lo])
+    is3 = (C.c_float * 3)(*[float(v) for v in grid.inv_step])
+    d3 = (C.c_int32 * 3)(nx, ny, nz)
+    L.check(L.load().nnr_render_sparse(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(view_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), lo3, is3, d3,
+                                       L.ptr(bits), L.ptr(packed), L.ptr(out), L.ptr(count), L.ptr(cell), L.ptr(out4), L.stream()),
+            "nnr_render_sparse")
+    res = (out[:, :3], out[:, 3], out[:, 4])
+    return res + (count, cell, out4) if debug else res
+
+
+class ParamsStamp:
+    """What a packed-weights cache entry is valid for, for whoever derives something else from the parameters (the renderer's occupancy
+    grid): the very same tensor objects at the same in-place versions, with no optimizer step since."""
+
+    def __init__(self, weights, biases):
+        self._entry = _PackCache(None, [*weights, *biases], None)
+
+    def matches(self, weights, biases):
+        return self._entry.matches(None, [*weights, *biases])
+
+
 def tsdf_integrate(origin, step, bricks: torch.Tensor, cams: torch.Tensor, depth: torch.Tensor, trunc: float, sum: torch.Tensor,
                    weight: torch.Tensor, z_min: float = 0.):
     """Integrate depth maps into the truncated signed distance accumulators of a list of 8 x 8 x 8 bricks of the grid (origin, step), IN PLACE,

@@ -6,7 +6,11 @@ one.  GPU only (the render path has no CPU fallback).
 
     python tools/scene_writer.py /tmp/scenes --frames 16 --size 120 160
     python tools/train_scene.py /tmp/scenes synthetic --epochs 200 [--style tanks|llff] [--host-loader] [--out result.json]
-                                [--checkpoint-dir DIR]
+                                [--checkpoint-dir DIR] [--occupancy RES ALPHA_MIN [ALPHA_MIN ...]]
+
+--occupancy: after the last epoch render full frames of training views dense and through rendering.occupancy (the sparse inference render) and
+print, per ALPHA_MIN, the share of samples culled and the PSNR of the sparse against the dense frames (style tanks: the grid covers the cube
+of rendering.radius).
 
 --checkpoint-dir: after the last epoch write model.pt, model_pose.pt (and model_focal.pt where a focal is learnt) there through
 CheckpointIO, in the layout train.py writes and tools/extract_mesh.py loads (save_checkpoints), next to config.yaml: the run's whole
@@ -58,6 +62,10 @@ def scene_cfg(path, scene, style="tanks", n_rays=1024, n_samples=128, hidden=256
             "with_auto_mask": False, "learning_rate": 1e-3, "pose_lr": 5e-4, "distortion_lr": 5e-4,
         },
     }
+
+
+def num_fine_of(cfg):
+    return int(cfg["rendering"].get("num_fine", 0) or 0)
 
 
 def build(cfg, device, n_views):
@@ -138,7 +146,74 @@ def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_poi
             "seconds_per_frame": dt / max(1, len(rows))}
 
 
-def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=None, eval_epochs=0, eval_dir=None, checkpoint_dir=None, **cfg_kw):
+def occupancy_compare(cfg, nope, pose, loader, field, device, resolution, alpha_mins, dilate=1, bounds=None, frames=4):
+    """Full frames of the first `frames` training views at their learned poses, rendered dense and with rendering.occupancy (the sparse
+    inference render) for every alpha_min -> rows of {alpha_min, cells occupied, samples culled, PSNR of the sparse
+    against the dense frames, seconds per frame of both}.  The culled share is counted by a debug call of nnr.ops.render_sparse on the
+    frames' rays; the timed renders run without it."""
+    import model as mdl
+    from model import imaging
+    from nnr import camera
+    from nnr import ops
+    from model.common import arange_pixels, mse2psnr
+    base = nope.renderer
+    base.eval()
+    views = []
+    for batch in loader:
+        if len(views) >= frames:
+            break
+        views.append((batch["img.camera_mat"].to(device), batch["img.scale_mat"].to(device), int(batch["img.idx"])))
+    with torch.no_grad():
+        mats = [(cam, imaging.inverse_pose(pose(i)), scale) for cam, scale, i in views]
+    size = (field.H, field.W)
+
+    def frames_of(renderer):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = [imaging.render_full_image(renderer, size, cam, world, scale, "nope_nerf", device)[0] for cam, world, scale in mats]
+        torch.cuda.synchronize()
+        return torch.stack(out), (time.perf_counter() - t0) / len(mats)
+
+    frames_of(base)      # (lazy initialisations)
+    dense, t_dense = frames_of(base)
+    rows = []
+    for alpha_min in alpha_mins:
+        occ = {"resolution": int(resolution), "alpha_min": float(alpha_min), "dilate": int(dilate)}
+        if bounds is not None:
+            occ["bounds"] = list(bounds)
+        sparse_r = mdl.Renderer(base.model, dict(cfg["rendering"], occupancy=occ), device=device)
+        sparse_r.eval()
+        frames_of(sparse_r)      # (builds the grid)
+        sparse, t_sparse = frames_of(sparse_r)
+        grid = sparse_r.__dict__["_occupancy_hit"][2]
+        live = total = 0
+        with torch.no_grad():
+            pixels = arange_pixels(resolution=size, device=device)[1]
+            depth = torch.ones(1, pixels.shape[1], 1, device=device)
+            for cam, world, scale in mats:
+                origin, ray, view, _, _, _ = camera.ray_setup(pixels, depth, cam, world, scale, bool(cfg["rendering"]["normalise_ray"]),
+                                                              bool(cfg["rendering"]["use_ray_dir"]))
+                if cfg["rendering"]["sample_option"] == "ndc":
+                    origin, ray = camera.ndc_rays(origin, ray, cam, 1.0)
+                    z_lo, z_hi = sparse_r._z_tables(cfg["rendering"]["num_points"], 0., 1., False, device)
+                else:
+                    z_lo, z_hi = sparse_r._z_tables(cfg["rendering"]["num_points"], *base.depth_range, False, device)
+                net = base.model
+                count = ops.render_sparse(origin, ray, view, z_lo, z_hi, None, grid, net.weights(), net.biases(), hidden=net.hidden_dim,
+                                          dist_alpha=bool(cfg["rendering"]["dist_alpha"]), white_bg=False,
+                                          relu_sigma=(net.occ_activation != "softplus"), debug=True)[3]
+                live += int(count.sum())
+                total += count.numel() * int(z_lo.shape[0])
+        mse = float(torch.nn.functional.mse_loss(sparse, dense))
+        rows.append({"alpha_min": float(alpha_min), "resolution": int(resolution), "cells_occupied": float(grid.occupied),
+                     "samples_culled": 1. - live / max(total, 1), "psnr_sparse_vs_dense": float(mse2psnr(mse)) if mse > 0. else float("inf"),
+                     "seconds_per_frame_dense": t_dense, "seconds_per_frame_sparse": t_sparse, "frames": len(mats)})
+        print(json.dumps({"occupancy": rows[-1]}), flush=True)
+    return rows
+
+
+def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=None, eval_epochs=0, eval_dir=None, checkpoint_dir=None,
+        occupancy=None, **cfg_kw):
     """-> dict with the per-epoch PSNR / pose-error curve and the loop throughput (+ novel-view scores with eval_epochs > 0)."""
     import dataloading as dl
     from model.common import mse2psnr
@@ -186,7 +261,13 @@ def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=No
         import tempfile
         with tempfile.TemporaryDirectory() as tmp:
             novel = novel_view_eval(cfg, trainer.model, pose, field, device, eval_epochs, eval_dir or tmp, n_points=min(1024, n_rays))
-    return {"novel_views": novel, "scene": scene, "style": style, "views": n_views, "image": [field.H, field.W], "rays_per_step": n_rays,
+    occ_rows = None
+    if occupancy is not None:      # (resolution, [alpha_min, ...]): dense against sparse evaluation frames
+        if num_fine_of(cfg):
+            raise ValueError("--occupancy compares plain renders: leave --num-fine off")
+        occ_rows = occupancy_compare(cfg, trainer.model, pose, loader, field, device, occupancy[0], occupancy[1],
+                                     bounds=[[-1.5, -1.5, -1.], [1.5, 1.5, 1.]] if style == "llff" else None)
+    return {"novel_views": novel, "occupancy": occ_rows, "scene": scene, "style": style, "views": n_views, "image": [field.H, field.W], "rays_per_step": n_rays,
             "samples_per_ray": cfg["rendering"]["num_points"], "fine_samples_per_ray": cfg["rendering"].get("num_fine", 0), "proposal": cfg["rendering"].get("proposal", "render"), "hidden": cfg["model"]["hidden_dim"], "epochs": epochs,
             "steps": it + 1, "loader": "resident" if cfg["dataloading"]["resident"] else "host(workers=%d)" % cfg["dataloading"]["n_workers"],
             "aux_losses": cfg["training"]["pc_weight"][0] != 0.0,
@@ -211,15 +292,21 @@ def main():
     ap.add_argument("--num-fine", type=int, default=0, help="rendering.num_fine: fine samples per ray drawn from the coarse pass's weights (0 = off)")
     ap.add_argument("--proposal", choices=("render", "density"), default=None,
                     help="rendering.proposal (with --num-fine): 'render' = coarse forward + resampling launch (default), 'density' = the fused proposal kernel")
+    ap.add_argument("--occupancy", nargs="+", default=None, metavar=("RES", "ALPHA_MIN"),
+                    help="after training: render evaluation frames dense and with rendering.occupancy {resolution: RES, alpha_min: ALPHA_MIN} "
+                         "(several ALPHA_MIN: one row each); prints the culled share and the PSNR of the sparse against the dense frames")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--eval-epochs", type=int, default=0, help="test-time pose optimisation epochs before scoring the held-out views")
     ap.add_argument("--eval-dir", default=None, help="where the rendered held-out frames go (default: a temporary directory)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--checkpoint-dir", default=None, help="write model.pt, model_pose.pt and config.yaml here after the last epoch (tools/extract_mesh.py takes DIR/config.yaml)")
     a = ap.parse_args()
+    if a.occupancy is not None and len(a.occupancy) < 2:
+        ap.error("--occupancy RES ALPHA_MIN [ALPHA_MIN ...]")
+    occupancy = None if a.occupancy is None else (int(a.occupancy[0]), [float(v) for v in a.occupancy[1:]])
     res = run(a.path, a.scene, style=a.style, epochs=a.epochs, log_every=a.log_every, eval_epochs=a.eval_epochs, eval_dir=a.eval_dir, checkpoint_dir=a.checkpoint_dir, n_rays=a.rays, n_samples=a.samples,
               hidden=a.hidden, resident=not a.host_loader, aux=not a.no_aux, resize_factor=a.factor, workers=a.workers,
-              mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine, proposal=a.proposal)
+              mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine, proposal=a.proposal, occupancy=occupancy)
     print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
