@@ -25,7 +25,7 @@ SOURCES = [("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MOD
            ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256",)), ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=128",)),
            ("nnr_mlp_fwd_bf16.hip", ()), ("nnr_mlp_dgrad_bf16.hip", ()), ("nnr_mlp_fwd.hip", ()), ("nnr_mlp_dgrad.hip", ()), ("nnr_depth_f16.hip", ()),
-           ("nnr_api.cpp", ()), ("nnr_wgrad_plan.cpp", ()), ("nnr_fusion_api.cpp", ()), ("nnr_sparse_api.cpp", ()), ("nnr_tsdf.hip", ()), ("nnr_pack.hip", ()), ("nnr_wgrad_bf16.hip", ()), ("nnr_composite.hip", ()), ("nnr_resample.hip", ()),
+           ("nnr_api.cpp", ()), ("nnr_wgrad_plan.cpp", ()), ("nnr_fusion_api.cpp", ()), ("nnr_sparse_api.cpp", ()), ("nnr_regularise_api.cpp", ()), ("nnr_tsdf.hip", ()), ("nnr_pack.hip", ()), ("nnr_wgrad_bf16.hip", ()), ("nnr_composite.hip", ()), ("nnr_ray_distortion.hip", ()), ("nnr_resample.hip", ()),
            ("nnr_camera.hip", ()), ("nnr_pointcloud.hip", ()), ("nnr_aux.hip", ()), ("nnr_randperm.hip", ()), ("nnr_optim.hip", ())]
 
 
@@ -44,6 +44,9 @@ FUSION_API_ONLY = [os.path.join("..", "..", "include", "nnr_fusion.h")]      # t
 SPARSE_ONLY = ["nnr_sparse_kernels.h"]      # the sparse inference render's argument block and launcher: nnr_sparse_f16.hip and its host unit nnr_sparse_api.cpp
 SPARSE_UNITS = ("nnr_sparse_f16.hip", "nnr_sparse_api.cpp")
 SPARSE_API_ONLY = [os.path.join("..", "..", "include", "nnr_sparse.h")]      # the sparse render's entry point's header: nnr_sparse_api.cpp alone
+REGULARISE_ONLY = ["nnr_regularise_kernels.h"]      # the ray-distortion regulariser's argument block and launchers: nnr_ray_distortion.hip and its host unit nnr_regularise_api.cpp
+REGULARISE_UNITS = ("nnr_ray_distortion.hip", "nnr_regularise_api.cpp")
+REGULARISE_API_ONLY = [os.path.join("..", "..", "include", "nnr_regularise.h")]      # the regulariser's entry points' header: its two units alone
 PLAN_ONLY = ["nnr_wgrad_plan.h"]      # the host planners' header (no kernel includes it): nnr_api.cpp and nnr_wgrad_plan.cpp
 HEADERS = ["nnr_layout.h", "nnr_device.h", "nnr_kernels.h", "nnr_mlp_bf16.h", "nnr_split.h", os.path.join("..", "..", "include", "nnr.h")]
 # -pragma-unroll-threshold: the MLP kernels are straight-line code by construction (every `#pragma unroll` loop must unroll fully, or
@@ -63,6 +66,7 @@ SCRATCH_LIMIT = {"18mlp_fwd_f16_kernelI": 0, "18mlp_fwd_f16_kernelILi256ELb0E": 
                  "21mlp_dgrad_bf16_kernelI": 64, "20composite_fwd_kernelE": 0, "20composite_bwd_kernelE": 0,
                  "16march_f16_kernelI": 0, "19march_finish_kernel": 0, "15resample_kernelE": 0, "18propose_f16_kernelI": 0, "15grid_f16_kernelI": 0, "17bricks_f16_kernelI": 0,
                  "16depth_f16_kernelI": 0, "21tsdf_integrate_kernelE": 0,
+                 "25ray_distortion_fwd_kernelE": 0, "25ray_distortion_bwd_kernelE": 0,
                  "17sparse_f16_kernelI": 48}      # (the inference forward's passes and composite carry: its allowance)
 
 
@@ -138,6 +142,8 @@ def own_headers(src):
         own = own + SPARSE_ONLY
     if src == "nnr_sparse_api.cpp":
         own = own + SPARSE_API_ONLY
+    if src in REGULARISE_UNITS:
+        own = own + REGULARISE_ONLY + REGULARISE_API_ONLY
     return own
 
 

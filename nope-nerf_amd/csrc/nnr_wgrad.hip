@@ -1011,7 +1011,14 @@ __global__ __launch_bounds__(256, 1) void wgrad_kernel(WgradArgs a) {
                 }
             }
             if (__builtin_amdgcn_readfirstlane(jb.MI * 8 + jb.NI) == 4 * 8 + 4) {
-                f32x4* const stage = stage_all + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kStageF4;
+                // A wave's private staging area starts where its position-encoding area (wgrad_job_enc2, above) starts: a class-B workgroup may run
+                // both kinds of job at once on different waves (few samples: a wave's span of the tape covers several tiles), and with a stride of
+                // kStageF4 here and kEncStageF4 there wave 2's 32 KiB began 8 KiB inside wave 1's 36 KiB -- at D = 256 with 128 padded samples the
+                // merged colour tile and the skip layer's encoding tile overwrote each other's operands (wrong fc_feature / rgb_layers.0 gradients,
+                // different from run to run).  One stride for both; 4 x 36 KiB lie inside the workgroup jobs' 160 KiB.
+                constexpr int kPrivateF4 = F16 && kEncStageF4 > kStageF4 ? kEncStageF4 : kStageF4;
+                static_assert(kWavesPerBlock * kPrivateF4 <= (int)(sizeof(stage_all) / sizeof(f32x4)), "the four private staging areas fit in stage_all");
+                f32x4* const stage = stage_all + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kPrivateF4;
                 // (every gradient plane of the three-term mode is tile-major: WsLayout::tiled -- the row-major instantiation is not built)
                 switch (__builtin_amdgcn_readfirstlane(jb.bias)) {
                     case 2: wgrad_job_split<2, 4, kTileGradPlanes, kTileActPlanes>(jb, a, lane, ji, stage); break;

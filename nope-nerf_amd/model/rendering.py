@@ -87,6 +87,7 @@ class Renderer(nn.Module):
         self._z_cache = {}
         self.jitter_window = None   # (first ray, rays in the whole step) when this process renders a shard
         self.normal_window = None   # (validity of ALL rays of the step, first ray) for the normal term of a shard
+        self.ray_distortion = False   # set by the trainer for a step whose training.ray_distortion_weight is not 0: out['ray_distortion']
 
     def forward(self, pixels, depth, camera_mat, world_mat, scale_mat, rendering_technique, add_noise=True,
                 eval_=False, it=1000000, rays=None):
@@ -222,6 +223,17 @@ class Renderer(nn.Module):
                     _, _, alpha_c, z_c = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(), samples=True, **kw)
                 z_lo, z_hi = self._unit_tables(n_samples + n_fine, device)      # z = 0 + (1 - 0) * jitter: the kernels take the depths as given
                 jitter = _nnr_ops.resample(alpha_c, z_c, xi, n_fine)
+        # the ray distortion of the compositing weights (training.ray_distortion_weight; nnr_ray_distortion.hip): on the training render only,
+        # at depths normalised by the COARSE range, whatever num_fine added
+        ray_distortion = None
+        if self.ray_distortion and torch.is_grad_enabled() and not eval_:
+            if not pixels.is_cuda:
+                raise NotImplementedError("training.ray_distortion_weight != 0 runs only on the GPU (HIP kernels, nnr_ray_distortion.hip); there "
+                                          "is no CPU ray distortion -- set training.ray_distortion_weight: 0 for CPU runs")
+            if cfg['sample_option'] == 'ndc':
+                ray_distortion = (0.0, 1.0)
+            else:
+                ray_distortion = (float(self.depth_range[0]), 1.0 / (float(self.depth_range[1]) - float(self.depth_range[0])))
         lazy_samples = not torch.is_grad_enabled()   # evaluation / visualisation: per-sample outputs only if somebody reads them
         grid = self._occupancy_grid(pixels, z_lo, kw) if cfg.get('occupancy', None) is not None else None
         if grid is not None:
@@ -231,6 +243,11 @@ class Renderer(nn.Module):
                                                        hidden=kw['hidden'], dist_alpha=kw['dist_alpha'], white_bg=kw['white_bg'],
                                                        relu_sigma=kw['relu_sigma'])
             alpha = z_val = None
+        elif ray_distortion is not None:
+            rgb, dist_pred, alpha, z_val, dloss = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(),
+                                                                  samples=not lazy_samples, ray_distortion=ray_distortion, **kw)
+            if dloss is None:
+                raise RuntimeError("training.ray_distortion_weight != 0, but nothing the render depends on requires a gradient")
         else:
             rgb, dist_pred, alpha, z_val = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(),
                                                            samples=not lazy_samples, **kw)
@@ -252,6 +269,7 @@ class Renderer(nn.Module):
             'd_gt_dense': d_gt,
             'mask': object_mask,
             'ndc': cfg['sample_option'] == 'ndc',
+            **({'ray_distortion': dloss} if ray_distortion is not None else {}),
         })
 
     # ------------------------------------------------------------------------------------------------ sparse inference render

@@ -102,6 +102,14 @@ class Trainer(object):
         self.vis_geo = cfg['vis_geo']
         for k in _CFG_KEYS + _WEIGHT_KEYS:
             setattr(self, k, cfg[k])
+        # training.ray_distortion_weight (absent or 0 = off: nothing below changes): the weight of the ray distortion of the compositing weights
+        # (nnr_ray_distortion.hip through nnr.render_rays), a scalar or [start, end] annealed like the other weights
+        rd = cfg.get('ray_distortion_weight', None)
+        rd = [0.0, 0.0] if rd is None else [float(v) for v in rd] if isinstance(rd, (list, tuple)) else [float(rd), float(rd)]
+        if len(rd) != 2:
+            raise ValueError("training.ray_distortion_weight: a scalar or [start, end], got %r" % (cfg.get('ray_distortion_weight'),))
+        self.ray_distortion_weight = rd
+        self._rd_weight = 0.0      # this step's annealed value (compute_loss)
         self.loss = Loss(cfg)
         self._warned_geo = False
         self._one = None
@@ -270,7 +278,11 @@ class Trainer(object):
         weights = {k: self.anneal(getattr(self, k)[0], getattr(self, k)[1], scheduling_start, self.annealing_epochs, epoch)
                    for k in _WEIGHT_KEYS}
         rgb_loss_type = 'l1' if epoch < self.annealing_epochs + scheduling_start else 'l2'
-        render_model = weights['rgb_weight'] != 0.0 or weights['depth_weight'] != 0.0
+        self._rd_weight = 0.0
+        if self.ray_distortion_weight != [0.0, 0.0] and not eval_mode:
+            self._rd_weight = float(self.anneal(self.ray_distortion_weight[0], self.ray_distortion_weight[1], scheduling_start,
+                                                self.annealing_epochs, epoch))
+        render_model = weights['rgb_weight'] != 0.0 or weights['depth_weight'] != 0.0 or self._rd_weight != 0.0      # (the term needs the render)
         use_ref_imgs = weights['pc_weight'] != 0.0 or weights['rgb_s_weight'] != 0.0
         world, rank = parallel.world_size(), parallel.rank()
 
@@ -354,15 +366,19 @@ class Trainer(object):
             renderer = self.model.renderer
             renderer.jitter_window = (lo, n_total) if world > 1 else None
             renderer.normal_window = None
+            renderer.ray_distortion = self._rd_weight != 0.0      # the training render of this step returns out['ray_distortion'] (R,)
             if world > 1 and renderer.cfg.get('normal_loss'):
                 # the normal term perturbs one surface point per VALID ray: the shard needs the validity of all rays to find its rows
                 with torch.no_grad():
                     d_all = self._gather_depth_all(depth_input, ray_idx, (h, w), depth_affine)
                 renderer.normal_window = (torch.isfinite(d_all) & (d_all != 0), lo)
-            out = self.model(p, ray_loc, camera_mat, world_mat, scale_mat, self.rendering_technique, it=it,
-                             eval_mode=eval_mode, depth_img=depth_input, img_size=(h, w), depth_affine=depth_affine,
-                             **({'rays': tuple(rays)} if rays is not None else {}))
-            renderer.jitter_window = renderer.normal_window = None
+            try:
+                out = self.model(p, ray_loc, camera_mat, world_mat, scale_mat, self.rendering_technique, it=it,
+                                 eval_mode=eval_mode, depth_img=depth_input, img_size=(h, w), depth_affine=depth_affine,
+                                 **({'rays': tuple(rays)} if rays is not None else {}))
+            finally:      # (the renderer is shared with evaluation: a render that raises must not leave the step's switches set)
+                renderer.jitter_window = renderer.normal_window = None
+                renderer.ray_distortion = False
             rendered_rgb = out['rgb']
             if not (rendered_rgb.is_cuda and self.loss.depth_loss_type == 'l1'):
                 rendered_depth, gt_depth = out['depth_pred'], out['depth_gt']     # masked views, only where the torch loss needs them
@@ -437,6 +453,10 @@ class Trainer(object):
         fused = (out is not None and rgb.is_cuda and self.loss.depth_loss_type == 'l1' and 'dist_dense' in out)
         if not fused and world == 1:
             loss_dict = self.loss(rgb, rgb_gt, depth_pred, depth_gt, **kwargs)
+            rd = self._ray_distortion_of(out)
+            if rd is not None:
+                loss_dict['loss_ray_distortion'] = rd.sum() / float(n_total)
+                loss_dict['loss'] = loss_dict['loss'] + self._rd_weight * loss_dict['loss_ray_distortion']
             return loss_dict
         aux, parts = self.loss.aux_terms(rgb_gt, **kwargs)
         if world > 1:
@@ -488,9 +508,22 @@ class Trainer(object):
                     if w['depth_weight'] != 0.0 else zero
             l2 = (diff * diff).sum() / float(3 * n_total) if (w['rgb_weight'] != 0.0 or w['depth_weight'] != 0.0) else zero
             lmain = w['rgb_weight'] * lrgb + w['depth_weight'] * ldep
-        loss_dict.update(loss_rgb=lrgb, loss_depth=ldep, l2_mean=l2, loss=lmain if aux is None else lmain + aux)
+        total = lmain if aux is None else lmain + aux
+        rd = self._ray_distortion_of(out)
+        if rd is not None:
+            # per ray, divided by the GLOBAL ray count like the rgb term: the sum over data-parallel ranks is the single-process loss
+            loss_dict['loss_ray_distortion'] = rd.sum() / float(n_total)
+            total = total + self._rd_weight * loss_dict['loss_ray_distortion']
+        loss_dict.update(loss_rgb=lrgb, loss_depth=ldep, l2_mean=l2, loss=total)
         self._check_nan(loss_dict['loss'])
         return loss_dict
+
+    def _ray_distortion_of(self, out):
+        """The step's per-ray distortion (R,), or None where the term is off or the render has none: only Renderer.nope_nerf makes it (the
+        phong renderer is not affected by training.ray_distortion_weight)."""
+        if self._rd_weight == 0.0 or out is None:
+            return None
+        return out.get('ray_distortion', None)
 
     @staticmethod
     def _gather_depth_all(depth_input, ray_idx, img_size, depth_affine):

@@ -227,18 +227,28 @@ class _RenderRays(torch.autograd.Function):
         L.check(lib.nnr_render_fwd(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(view_d), L.ptr(z_lo), L.ptr(z_hi),
                                    L.ptr(jit), L.ptr(packed), L.ptr(rgb), L.ptr(dist), L.ptr(alpha), L.ptr(zv), L.ptr(ws), st),
                 "nnr_render_fwd")
+        rd = opts.get("ray_distortion", None)
+        dloss = None      # (stays None where nothing is to be differentiated: no launch, no fifth value)
+        if rd is not None and need_grad:
+            # the ray distortion of the weights (nnr_ray_distortion.hip), read off the kept workspace: sigma_raw is column 3 of plane 0, z plane 1
+            dloss = torch.empty(R, **f32)
+            L.check(lib.nnr_ray_distortion_fwd(C.byref(cfg), _ws_column(cfg, ws, 0, 3), 4, _ws_column(cfg, ws, 1, 0), rd[0], rd[1],
+                                               L.ptr(dloss), st), "nnr_ray_distortion_fwd")
         if need_grad:
             ctx.cfg, ctx.ws, ctx.packed, ctx.dev = cfg, ws, packed, dev
             ctx.shapes = [tuple(p.shape) for p in params]
+            ctx.ray_distortion = rd
         else:
             _give_workspace(cfg, dev, ws)
         if want_samples:
             ctx.mark_non_differentiable(alpha, zv)
         ctx.set_materialize_grads(False)      # undefined upstream gradients arrive as None, not as zero-filled tensors
+        if rd is not None:
+            return rgb, dist, alpha, zv, dloss
         return rgb, dist, alpha, zv
 
     @staticmethod
-    def backward(ctx, d_rgb, d_dist, _da, _dz):
+    def backward(ctx, d_rgb, d_dist, _da, _dz, d_dloss=None):
         cfg, ws, dev = ctx.cfg, ctx.ws, ctx.dev
         if ws is None:
             raise RuntimeError("nnr: backward called twice on the same render (workspace already released)")
@@ -251,6 +261,12 @@ class _RenderRays(torch.autograd.Function):
         need_w = any(ctx.needs_input_grad[7:])
         need_rays = any(ctx.needs_input_grad[:3])
         L.check(lib.nnr_composite_bwd(C.byref(cfg), L.ptr(d_rgb), L.ptr(d_dist), L.ptr(ws), st), "nnr_composite_bwd")
+        if d_dloss is not None:
+            # the regulariser's d(sigma_raw) joins the compositor's in column 3 of plane 2, before the MLP's backward reads it
+            rd = ctx.ray_distortion
+            d_dloss = d_dloss.contiguous().float()
+            L.check(lib.nnr_ray_distortion_bwd(C.byref(cfg), _ws_column(cfg, ws, 0, 3), 4, _ws_column(cfg, ws, 1, 0), rd[0], rd[1],
+                                               L.ptr(d_dloss), _ws_column(cfg, ws, 2, 3), 4, 1, st), "nnr_ray_distortion_bwd")
         L.check(lib.nnr_mlp_dgrad(C.byref(cfg), L.ptr(ctx.packed), L.ptr(ws), st), "nnr_mlp_dgrad")
         grads: List[Optional[torch.Tensor]] = [None] * (2 * L.N_LAYERS)
         if need_w:
@@ -281,6 +297,23 @@ class _RenderRays(torch.autograd.Function):
         return (d_o, d_d, d_v, None, None, None, None, *grads)
 
 
+def _ws_column(cfg: L.Cfg, ws: torch.Tensor, plane: int, col: int):
+    """Device pointer of column `col` of a row-major fp32 workspace plane (nnr_ws_plane's offset)."""
+    pitch = C.c_int32(0)
+    off = L.load().nnr_ws_plane(C.byref(cfg), plane, C.byref(pitch))
+    if off < 0 or col >= pitch.value or L.load().nnr_ws_plane_layout(C.byref(cfg), plane) != 0:
+        raise RuntimeError("nnr: workspace plane %d has no row-major column %d" % (plane, col))
+    return C.c_void_p(ws.data_ptr() + 4 * (off + col))
+
+
+def _ray_distortion_range(rd):
+    """(s_near, s_inv) of render_rays(ray_distortion=...) as two host floats; a value the kernels would refuse is refused here."""
+    s_near, s_inv = float(rd[0]), float(rd[1])
+    if not (np.isfinite(s_near) and np.isfinite(s_inv) and s_inv > 0.0):
+        raise ValueError("nnr: ray_distortion=(s_near, s_inv) needs finite values and s_inv > 0, got %r" % ((s_near, s_inv),))
+    return s_near, s_inv
+
+
 GRAD_TAIL = 2048      # spare floats behind the flat weight-gradient buffer (see _RenderRays.backward)
 _flat_grads = {}      # storage data_ptr -> (weak reference to the flat buffer, floats used by the gradient views): buffers _RenderRays.backward made
 
@@ -302,19 +335,85 @@ def flat_grads_of(storage_ptr: int):
 
 def render_rays(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor,
                 jitter: Optional[torch.Tensor], weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], *,
-                hidden: int, dist_alpha: bool, white_bg: bool, relu_sigma: bool, bf16: bool = False, samples: bool = True):
+                hidden: int, dist_alpha: bool, white_bg: bool, relu_sigma: bool, bf16: bool = False, samples: bool = True,
+                ray_distortion=None):
     """(R,3) sampling origin / direction / view direction, (N) z interval tables, optional (R,N) jitter, the 12
     nn.Linear weights and biases in state_dict order  ->  rgb (R,3), dist (R), alpha (R,N), z (R,N).
     Differentiable w.r.t. pts_o, pts_d, view_d, weights, biases.  bf16: bf16-MFMA products (fp32 accumulation) in the MLP
     forward and input-gradient kernels (NNR_F_BF16); weight gradients stay fp32.  samples=False (only honoured under torch.no_grad):
-    alpha and z come back as None and the renderer composites inside the MLP kernel (16 bytes written per ray)."""
+    alpha and z come back as None and the renderer composites inside the MLP kernel (16 bytes written per ray).
+    ray_distortion=(s_near, s_inv) (default None: nothing changes): where gradients are needed, a fifth, differentiable output dloss (R,), the
+    ray distortion of every ray's compositing weights at the normalised depths (z - s_near) * s_inv (include/nnr_regularise.h); its gradient
+    reaches everything the other outputs' do.  Without gradients (torch.no_grad, or no input that requires one) the fifth output is None."""
     opts = dict(hidden=hidden, dist_alpha=dist_alpha, white_bg=white_bg, relu_sigma=relu_sigma, bf16=bool(bf16), samples=bool(samples),
                 params=(list(weights), list(biases)))    # the caller's own tensor objects: identity keys the pack cache
+    if ray_distortion is not None:
+        opts["ray_distortion"] = _ray_distortion_range(ray_distortion)
     if not torch.is_grad_enabled():
         # forward-only (eval / visualisation inside torch.no_grad): no stash, small workspace
         return _RenderRays.apply(pts_o.detach(), pts_d.detach(), view_d.detach(), z_lo, z_hi, jitter, opts,
                                  *[w.detach() for w in weights], *[b.detach() for b in biases])
     return _RenderRays.apply(pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts, *weights, *biases)
+
+
+def _ray_distortion_inputs(raw, z):
+    _require_gpu(raw)
+    _require_gpu(z)
+    if raw.dim() != 2 or z.shape != raw.shape or raw.dtype != torch.float32 or z.dtype != torch.float32:
+        raise ValueError("nnr: ray_distortion takes fp32 raw and z of one shape (R, N), got %r %s and %r %s"
+                         % (tuple(raw.shape), raw.dtype, tuple(z.shape), z.dtype))
+    if not z.is_contiguous():
+        raise ValueError("nnr: ray_distortion: z must be contiguous")
+    return _sample_stride(raw)
+
+
+def _sample_stride(t: torch.Tensor) -> int:
+    """Floats between consecutive samples of an (R, N) tensor whose element (r, j) sits (r N + j) strides behind the first."""
+    R, N = t.shape
+    s = t.stride(1) if N > 1 else (t.stride(0) if R > 1 else 1)
+    if s < 1 or (R > 1 and t.stride(0) != s * N):
+        raise ValueError("nnr: ray_distortion: an (R, N) tensor with ONE stride between consecutive samples is needed (a contiguous tensor, "
+                         "or a column of an (R N, k) one viewed as (R, N)); got strides %r" % (tuple(t.stride()),))
+    return s
+
+
+def ray_distortion(raw: torch.Tensor, z: torch.Tensor, s_near: float, s_inv: float, dist_alpha: bool, relu_sigma: bool) -> torch.Tensor:
+    """The ray distortion of (R, N) fp32 densities-before-activation `raw` at depths `z` (non-decreasing along a ray): loss (R,), the kernel of
+    include/nnr_regularise.h alone on plain tensors (tests and tools; training goes through render_rays(ray_distortion=...)).  `raw` may be
+    a strided view with one stride between samples: t[:, c].view(R, N) of an (R N, k) tensor.  No autograd: see ray_distortion_grad."""
+    stride = _ray_distortion_inputs(raw, z)
+    R, N = raw.shape
+    cfg = L.make_cfg(R, N, 0, dist_alpha=dist_alpha, relu_sigma=relu_sigma)
+    loss = torch.empty(R, dtype=torch.float32, device=raw.device)
+    s_near, s_inv = _ray_distortion_range((s_near, s_inv))
+    L.check(L.load().nnr_ray_distortion_fwd(C.byref(cfg), C.c_void_p(raw.data_ptr()), stride, L.ptr(z), s_near, s_inv, L.ptr(loss), L.stream()),
+            "nnr_ray_distortion_fwd")
+    return loss
+
+
+def ray_distortion_grad(raw: torch.Tensor, z: torch.Tensor, s_near: float, s_inv: float, dist_alpha: bool, relu_sigma: bool, g: torch.Tensor,
+                        out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """g_r d(loss_r)/d(raw_rj) of ray_distortion, (R, N) fp32.  `out` (default: a new contiguous tensor): where to write, laid out like `raw`
+    may be; accumulate=True adds to what `out` holds (the sum formed in double, rounded once) instead of overwriting."""
+    stride = _ray_distortion_inputs(raw, z)
+    R, N = raw.shape
+    _require_gpu(g)
+    if g.shape != (R,) or g.dtype != torch.float32:
+        raise ValueError("nnr: ray_distortion_grad: g must be fp32 of shape (R,)")
+    if out is None:
+        if accumulate:
+            raise ValueError("nnr: ray_distortion_grad: accumulate=True needs `out`")
+        out = torch.empty(R, N, dtype=torch.float32, device=raw.device)
+    if out.shape != raw.shape or out.dtype != torch.float32:
+        raise ValueError("nnr: ray_distortion_grad: out must be fp32 of raw's shape")
+    _require_gpu(out)
+    out_stride = _sample_stride(out)
+    cfg = L.make_cfg(R, N, 0, dist_alpha=dist_alpha, relu_sigma=relu_sigma)
+    s_near, s_inv = _ray_distortion_range((s_near, s_inv))
+    L.check(L.load().nnr_ray_distortion_bwd(C.byref(cfg), C.c_void_p(raw.data_ptr()), stride, L.ptr(z), s_near, s_inv, L.ptr(g.contiguous()),
+                                            C.c_void_p(out.data_ptr()), out_stride, int(bool(accumulate)), L.stream()),
+            "nnr_ray_distortion_bwd")
+    return out
 
 
 def mlp_points(pts: torch.Tensor, view: torch.Tensor, weights, biases, *, hidden: int, split2: bool = False):

@@ -122,7 +122,7 @@ def gather_rays(local: torch.Tensor, n_total: int) -> torch.Tensor:
 
 
 _LOGGED = ('loss', 'loss_rgb', 'loss_depth', 'l2_mean', 'loss_dist_1st', 'loss_dist_2nd', 'loss_pc', 'loss_rgb_s',
-           'loss_depth_consistency')
+           'loss_depth_consistency', 'loss_ray_distortion')
 
 
 def _shared_buffer(params):

@@ -6,11 +6,14 @@ one.  GPU only (the render path has no CPU fallback).
 
     python tools/scene_writer.py /tmp/scenes --frames 16 --size 120 160
     python tools/train_scene.py /tmp/scenes synthetic --epochs 200 [--style tanks|llff] [--host-loader] [--out result.json]
-                                [--checkpoint-dir DIR] [--occupancy RES ALPHA_MIN [ALPHA_MIN ...]]
+                                [--checkpoint-dir DIR] [--occupancy RES ALPHA_MIN [ALPHA_MIN ...]] [--ray-distortion W]
 
 --occupancy: after the last epoch render full frames of training views dense and through rendering.occupancy (the sparse inference render) and
 print, per ALPHA_MIN, the share of samples culled and the PSNR of the sparse against the dense frames (style tanks: the grid covers the cube
 of rendering.radius).
+
+--ray-distortion W: training.ray_distortion_weight = W, the weight of the ray distortion of the compositing weights (DESIGN.md section 13;
+0 = off, the default; the paper's example is 0.01).  The last logged line then carries the epoch's mean loss_ray_distortion.
 
 --checkpoint-dir: after the last epoch write model.pt, model_pose.pt (and model_focal.pt where a focal is learnt) there through
 CheckpointIO, in the layout train.py writes and tools/extract_mesh.py loads (save_checkpoints), next to config.yaml: the run's whole
@@ -33,7 +36,7 @@ import torch
 
 
 def scene_cfg(path, scene, style="tanks", n_rays=1024, n_samples=128, hidden=256, resident=True, aux=True, resize_factor=None,
-              sample_rate=8, workers=0, mfma_dtype="fp32", num_fine=0, proposal=None):
+              sample_rate=8, workers=0, mfma_dtype="fp32", num_fine=0, proposal=None, ray_distortion=0.0):
     """The keys configs/default.yaml + configs/Tanks/*.yaml (style 'tanks') or configs/LLFF/fern.yaml (style 'llff') would set."""
     llff = style == "llff"
     on = [1.0, 0.0] if aux else [0.0, 0.0]
@@ -60,6 +63,7 @@ def scene_cfg(path, scene, style="tanks", n_rays=1024, n_samples=128, hidden=256
             "depth_weight": [0.04, 0.0], "pc_weight": on, "rgb_s_weight": on, "depth_consistency_weight": [0.0, 0.0],
             "weight_dist_2nd_loss": [0.0, 0.0], "weight_dist_1st_loss": [0.0, 0.0], "depth_loss_type": "l1", "with_ssim": False,
             "with_auto_mask": False, "learning_rate": 1e-3, "pose_lr": 5e-4, "distortion_lr": 5e-4,
+            **({"ray_distortion_weight": float(ray_distortion)} if ray_distortion else {}),
         },
     }
 
@@ -231,19 +235,22 @@ def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=No
     curve = [dict(epoch=-1, psnr=None, **pose_errors(pose, gt, n_views))]
     it, t_loop, steps_timed = -1, 0.0, 0
     for epoch in range(epochs):
-        l2 = []
+        l2, rd = [], []
         sync()
         t0 = time.perf_counter()
         for batch in loader:
             it += 1
             losses = trainer.train_step(batch, it, epoch, 10 ** 6, None)
             l2.append(losses["l2_mean"])
+            if "loss_ray_distortion" in losses:
+                rd.append(losses["loss_ray_distortion"])
         mse = float(torch.stack(l2).detach().mean())             # the epoch's only device->host sync
         if epoch > 0:                                            # epoch 0 pays the lazy initialisations
             t_loop += time.perf_counter() - t0
             steps_timed += len(l2)
         if epoch % log_every == 0 or epoch == epochs - 1:
-            curve.append(dict(epoch=epoch, psnr=float(mse2psnr(mse)), **pose_errors(pose, gt, n_views)))
+            curve.append(dict(epoch=epoch, psnr=float(mse2psnr(mse)), **pose_errors(pose, gt, n_views),
+                              **({"ray_distortion": float(torch.stack([torch.as_tensor(v).detach().reshape(()) for v in rd]).mean())} if rd else {})))
             if parallel.rank() == 0:
                 print(json.dumps(curve[-1]), flush=True)
     trainer.flush_nan_check()        # the step's NaN check is one step late by design: look at the last one too
@@ -270,7 +277,7 @@ def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=No
     return {"novel_views": novel, "occupancy": occ_rows, "scene": scene, "style": style, "views": n_views, "image": [field.H, field.W], "rays_per_step": n_rays,
             "samples_per_ray": cfg["rendering"]["num_points"], "fine_samples_per_ray": cfg["rendering"].get("num_fine", 0), "proposal": cfg["rendering"].get("proposal", "render"), "hidden": cfg["model"]["hidden_dim"], "epochs": epochs,
             "steps": it + 1, "loader": "resident" if cfg["dataloading"]["resident"] else "host(workers=%d)" % cfg["dataloading"]["n_workers"],
-            "aux_losses": cfg["training"]["pc_weight"][0] != 0.0,
+            "aux_losses": cfg["training"]["pc_weight"][0] != 0.0, "ray_distortion_weight": cfg["training"].get("ray_distortion_weight", 0.0),
             "steps_per_s": steps_timed / t_loop if t_loop else None, "rays_per_s": steps_timed * n_rays / t_loop if t_loop else None,
             "curve": curve}
 
@@ -295,6 +302,8 @@ def main():
     ap.add_argument("--occupancy", nargs="+", default=None, metavar=("RES", "ALPHA_MIN"),
                     help="after training: render evaluation frames dense and with rendering.occupancy {resolution: RES, alpha_min: ALPHA_MIN} "
                          "(several ALPHA_MIN: one row each); prints the culled share and the PSNR of the sparse against the dense frames")
+    ap.add_argument("--ray-distortion", type=float, default=0.0, metavar="W",
+                    help="training.ray_distortion_weight: the weight of the ray distortion of the compositing weights (0 = off; e.g. 0.01)")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--eval-epochs", type=int, default=0, help="test-time pose optimisation epochs before scoring the held-out views")
     ap.add_argument("--eval-dir", default=None, help="where the rendered held-out frames go (default: a temporary directory)")
@@ -306,7 +315,8 @@ def main():
     occupancy = None if a.occupancy is None else (int(a.occupancy[0]), [float(v) for v in a.occupancy[1:]])
     res = run(a.path, a.scene, style=a.style, epochs=a.epochs, log_every=a.log_every, eval_epochs=a.eval_epochs, eval_dir=a.eval_dir, checkpoint_dir=a.checkpoint_dir, n_rays=a.rays, n_samples=a.samples,
               hidden=a.hidden, resident=not a.host_loader, aux=not a.no_aux, resize_factor=a.factor, workers=a.workers,
-              mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine, proposal=a.proposal, occupancy=occupancy)
+              mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine, proposal=a.proposal, occupancy=occupancy,
+              ray_distortion=a.ray_distortion)
     print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
