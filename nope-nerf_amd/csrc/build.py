@@ -3,6 +3,7 @@
 hipcc cross-compiles without a GPU.  Objects go to csrc/build/, the library to nope-nerf_amd/nnr/libnnr.so
 (git-ignored, but shipped to the GPU box by gpurun)."""
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -32,23 +33,8 @@ SOURCES = [("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MOD
 def _obj_name(src, defines):
     tag = "".join("_" + d.split("=")[0].lower().replace("nnr_", "") + d.split("=")[1] for d in defines)
     return os.path.splitext(src)[0] + tag + ".o"
-SPLIT2_ONLY = ["nnr_split2.h", "nnr_trunk_f16.h", "nnr_trunk_f16.inc"]      # included by the fp16-term kernels (the `_f16` units: forward, input gradient, march, proposal, grid, bricks, depth, sparse) only: touching them does not rebuild the rest (minutes per unit)
-DENSITY_ONLY = ["nnr_density_setup_f16.inc", "nnr_density_pass_f16.inc"]      # the density-only pass of the march, proposal, grid, bricks and depth kernels: touching it rebuilds those five units, not the forward and input-gradient `_f16` units
-DENSITY_UNITS = ("nnr_march_f16.hip", "nnr_propose_f16.hip", "nnr_grid_f16.hip", "nnr_bricks_f16.hip", "nnr_depth_f16.hip")
-ROW_ONLY = ["nnr_resample_row.h"]      # the row code of hierarchical sampling: nnr_resample.hip and nnr_propose_f16.hip
-FWD_ONLY = ["nnr_mlp_fwd_common.h"]      # included by nnr_mlp_fwd.hip and, through nnr_trunk_f16.h, by the `_f16` units
-GEOMETRY_ONLY = [os.path.join("..", "..", "include", "nnr_geometry.h")]      # the geometry-side entry points' header: nnr_api.cpp alone
-FUSION_ONLY = ["nnr_fusion_kernels.h"]      # the depth-fusion side's argument blocks and launchers: nnr_depth_f16.hip, nnr_tsdf.hip and their host unit nnr_fusion_api.cpp
-FUSION_UNITS = ("nnr_depth_f16.hip", "nnr_tsdf.hip", "nnr_fusion_api.cpp")
-FUSION_API_ONLY = [os.path.join("..", "..", "include", "nnr_fusion.h")]      # the depth-fusion entry points' header: nnr_fusion_api.cpp alone
-SPARSE_ONLY = ["nnr_sparse_kernels.h"]      # the sparse inference render's argument block and launcher: nnr_sparse_f16.hip and its host unit nnr_sparse_api.cpp
-SPARSE_UNITS = ("nnr_sparse_f16.hip", "nnr_sparse_api.cpp")
-SPARSE_API_ONLY = [os.path.join("..", "..", "include", "nnr_sparse.h")]      # the sparse render's entry point's header: nnr_sparse_api.cpp alone
-REGULARISE_ONLY = ["nnr_regularise_kernels.h"]      # the ray-distortion regulariser's argument block and launchers: nnr_ray_distortion.hip and its host unit nnr_regularise_api.cpp
-REGULARISE_UNITS = ("nnr_ray_distortion.hip", "nnr_regularise_api.cpp")
-REGULARISE_API_ONLY = [os.path.join("..", "..", "include", "nnr_regularise.h")]      # the regulariser's entry points' header: its two units alone
-PLAN_ONLY = ["nnr_wgrad_plan.h"]      # the host planners' header (no kernel includes it): nnr_api.cpp and nnr_wgrad_plan.cpp
-HEADERS = ["nnr_layout.h", "nnr_device.h", "nnr_kernels.h", "nnr_mlp_bf16.h", "nnr_split.h", os.path.join("..", "..", "include", "nnr.h")]
+
+
 # -pragma-unroll-threshold: the MLP kernels are straight-line code by construction (every `#pragma unroll` loop must unroll fully, or
 # the register arrays they index fall back to scratch memory).  LLVM caps `#pragma unroll` at 16 K instructions per loop; one GEMM part
 # of the fp32 input-gradient kernel sat right at that cap, and an unrelated clean-up pushed it over: the kernel compiled without a
@@ -123,28 +109,37 @@ def build_variant(name, defines, only=None):
     return out
 
 
-def own_headers(src):
-    """The headers beyond HEADERS that a source includes (file names in csrc/): what else makes its objects stale."""
-    own = SPLIT2_ONLY + FWD_ONLY if "_f16" in src else FWD_ONLY if src == "nnr_mlp_fwd.hip" else []
-    if src in DENSITY_UNITS:
-        own = own + DENSITY_ONLY
-    if src in ("nnr_resample.hip", "nnr_propose_f16.hip"):
-        own = own + ROW_ONLY
-    if src in ("nnr_api.cpp", "nnr_wgrad_plan.cpp"):
-        own = own + PLAN_ONLY
-    if src == "nnr_api.cpp":
-        own = own + GEOMETRY_ONLY
-    if src in FUSION_UNITS:
-        own = own + FUSION_ONLY
-    if src == "nnr_fusion_api.cpp":
-        own = own + FUSION_API_ONLY
-    if src in SPARSE_UNITS:
-        own = own + SPARSE_ONLY
-    if src == "nnr_sparse_api.cpp":
-        own = own + SPARSE_API_ONLY
-    if src in REGULARISE_UNITS:
-        own = own + REGULARISE_ONLY + REGULARISE_API_ONLY
-    return own
+_INCLUDES = {}      # file -> the files its `#include "..."` lines name: every file is read once
+
+
+def _includes(path, root):
+    if path not in _INCLUDES:
+        dirs = (os.path.dirname(path), root, os.path.join(root, "..", "..", "include"))
+        found = []
+        with open(path) as f:
+            for n, line in enumerate(f, 1):
+                m = re.match(r'\s*#\s*include\s+"([^"]+)"', line)
+                if m:
+                    hits = [t for t in (os.path.normpath(os.path.join(d, m.group(1))) for d in dirs) if os.path.isfile(t)]
+                    if not hits:
+                        raise FileNotFoundError('%s:%d: #include "%s" is in none of %s' % (path, n, m.group(1), ", ".join(map(os.path.normpath, dirs))))
+                    found.append(hits[0])
+        _INCLUDES[path] = found
+    return _INCLUDES[path]
+
+
+def deps(src, root=HERE):
+    """Every file that csrc/<src> includes in quotes, directly or through another such file (absolute, normalised paths): what beside the
+    source makes its objects stale.  A name is looked up as hipcc does with FLAGS: in the including file's directory, then in csrc/ (`root`),
+    then in include/.  Includes in angle brackets are the toolchain's and are ignored, and so is conditional compilation: a superset only
+    rebuilds more.  A name found nowhere is an error, never skipped -- a dependency this scan misses links a stale object without a word."""
+    found, todo = [], [os.path.normpath(os.path.join(root, src))]
+    while todo:
+        for inc in _includes(todo.pop(), root):
+            if inc not in found:
+                found.append(inc)
+                todo.append(inc)
+    return found
 
 
 LAST_BUILD = {"compiled": [], "reused": [], "linked": False}      # what the newest build() call did (printed by __graft_entry__.build())
@@ -153,12 +148,10 @@ LAST_BUILD = {"compiled": [], "reused": [], "linked": False}      # what the new
 def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OUT_DIR, exist_ok=True)
-    hdrs = [os.path.join(HERE, h) for h in HEADERS]
     jobs = []
     for src, defines in SOURCES:
         obj = os.path.join(OUT_DIR, _obj_name(src, defines))
-        own = [os.path.join(HERE, h) for h in own_headers(src)]
-        if force or _stale(obj, [os.path.join(HERE, src)] + hdrs + own):
+        if force or _stale(obj, [os.path.join(HERE, src)] + deps(src)):
             jobs.append([hipcc] + FLAGS + ["-D" + d for d in defines] + ["-c", os.path.join(HERE, src), "-o", obj])
 
     def run(cmd):

@@ -2,7 +2,8 @@
 // nnr_march_f16.hip through nnr_trunk_f16.h: two-term mode) share word for word around their GEMM parts and whose move into a forceinlined function
 // leaves their listings as they are (tools/isa_listing.py): the accumulators' start at the bias, the mask words, the launch grid.
 // (Tried and NOT shared for that reason, hipcc 7.2: the rgb head -- operands of four commutative adds swap; the fused compositing as a carry
-// struct or over references -- the inference kernel's register allocation changes throughout.)
+// struct or over references -- the inference kernel's register allocation changes throughout.  The colour branch with the rgb head is shared by
+// the two-term forward and the sparse render as included text, nnr_colour_f16.inc, which keeps the listings: profiles/colour_refactor/.)
 #pragma once
 #include "nnr_device.h"
 #include "nnr_kernels.h"

@@ -11,7 +11,7 @@
 //     DMA: its rays get the background.
 //   * passes: lane `col` of both halves takes j = list[32 pass + col]; a slot past n_live is dead, takes a clamped index and is computed
 //     like any other (the waves of a workgroup walk the weight stream together).  Trunk: nnr_trunk_f16.inc, TRAIN = false.  The colour
-//     branch and the rgb head restate the inference forward's, as this file's own text.  A live sample's (r, g, b, raw) is the forward's bit
+//     branch and the rgb head are the inference forward's text, nnr_colour_f16.inc.  A live sample's (r, g, b, raw) is the forward's bit
 //     for bit, incl. the NaN of a sample that saw an activation outside fp16's range; a sample whose point is not finite is NaN (it is outside the
 //     grid, hence live: its ray comes out NaN).
 //   * compositing: the forward's fused epilogue on the compacted list.  alpha_j = sample_alpha(raw_j, z_{j+1} - z_j) with z_{j+1} the next
@@ -165,55 +165,8 @@ __global__ __launch_bounds__(256, 1) void sparse_f16_kernel(SparseArgs a) {
 #include "nnr_trunk_f16.inc"
     }
 
-    // colour hidden: g = relu(W' h8 + Wg[:, D:] gamma_4(v) + b'); its side work finishes hidden 8 (half B) incl. the density head's other half
-    uint32_t mwB[HW];
-    init_acc(accA, bias, L::bias_off(10), half);
-    clear_mask(mwB);
-    {
-        f32x2 keep = {0.f, 0.f};      // (a name NNR_FINISH takes from here)
-        const float inv = inv_scale<L>(bias, 7);
-        const char* const pl = xh(7);
-        gemm_part2<DT, HT, NP, 1, 0, 0, 0>(accA, ph, pm, pipe, p0(F_RGBH_F), NNR_FINISH(accB, NP, mwB, inv, pl, HR / 4, true));
-    }
-    flush_max<TRAIN>(st, 7, lane, mx, mxa);
-    const float sg = sg0 + sg1;
-    const float sigma_raw = sg + __shfl_xor(sg, 32, 64) + bias[L::bias_off(8)];
-    {
-        uint32_t dh[8], dm[8];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const u32x4 vh = __builtin_bit_cast(u32x4, park[(8 + q) * 64]), vm = __builtin_bit_cast(u32x4, park[(10 + q) * 64]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { dh[4 * q + i] = vh[i]; dm[4 * q + i] = vm[i]; }
-        }
-        gemm_part2<1, HT>(accA, dh, dm, pipe, p0(F_RGBH_D));
-    }
-    float g[HR];      // the colour-hidden activations stay fp32: the rgb head is a per-lane dot product
-    {
-        const float inv = inv_scale<L>(bias, 8);
-#pragma unroll
-        for (int r = 0; r < HR; r += 2) {
-            g[r] = relu1(accA[r >> 4][r & 15] * inv);
-            g[r + 1] = relu1(accA[(r + 1) >> 4][(r + 1) & 15] * inv);
-        }
-    }
-    // rgb head: 3 per-lane dot products over the lane's half of g, halves combined by one shuffle, then sigmoid
-    float rgbv[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* wc = bias + L::wrgb_off + (2 * c + half) * HR;
-        float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll
-        for (int q = 0; q < HR / 4; ++q) {
-            const f32x4 w4 = *reinterpret_cast<const f32x4*>(wc + 4 * q);
-            acc0 = fmaf(w4[0], g[4 * q], acc0);
-            acc1 = fmaf(w4[1], g[4 * q + 1], acc1);
-            acc0 = fmaf(w4[2], g[4 * q + 2], acc0);
-            acc1 = fmaf(w4[3], g[4 * q + 3], acc1);
-        }
-        const float part = acc0 + acc1;
-        rgbv[c] = part + __shfl_xor(part, 32, 64);
-    }
+    auto xg = []() -> const char* { return nullptr; };
+#include "nnr_colour_f16.inc"
     {
         const float* b = bias + L::bias_off(11);
         f32x4 o;

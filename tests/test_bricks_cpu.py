@@ -1,6 +1,6 @@
 """CPU: the density-bricks entry point of the C ABI (nnr_density_bricks, include/nnr_geometry.h, added under ABI 8) -- where it is declared and
-listed, version agreement, every error return reached with fake device pointers before anything is dereferenced or launched, the Python
-wrapper's refusal of CPU weights, and what the build script holds the new kernel to."""
+listed, version agreement, every error return reached with fake device pointers before anything is dereferenced or launched, and the Python
+wrapper's refusal of CPU weights.  (What the build script holds the kernel to: test_build_cpu.py.)"""
 import ctypes as C
 import os
 import re
@@ -122,41 +122,3 @@ def test_ops_density_bricks_raises_on_cpu_weights():
                                   'rendering': {'white_background': False, 'dist_alpha': False}})
     with pytest.raises(RuntimeError):
         ops.density_bricks((0., 0., 0.), (.1, .1, .1), torch.zeros(2, 3, dtype=torch.int32), net.weights(), net.biases(), hidden=128)
-
-
-def _build_module():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("nnr_build", os.path.join(ROOT, "nope-nerf_amd", "csrc", "build.py"))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    return b
-
-
-def test_the_build_holds_the_bricks_kernel_to_no_scratch():
-    b = _build_module()
-    assert b.SCRATCH_LIMIT["17bricks_f16_kernelI"] == 0 and ("nnr_bricks_f16.hip", ()) in b.SOURCES
-    remark = "remark: Function Name: _ZN3nnr17bricks_f16_kernelILi256EEEvNS_10BricksArgsE\nremark:     ScratchSize [bytes/lane]: %d\n"
-    b.check_resources(remark % 0, "bricks")
-    with pytest.raises(RuntimeError, match="scratch"):
-        b.check_resources(remark % 16, "bricks")
-
-
-def test_the_build_rebuilds_the_bricks_unit_for_the_shared_pass():
-    b = _build_module()
-    csrc = os.path.join(ROOT, "nope-nerf_amd", "csrc")
-    shared = ["nnr_density_setup_f16.inc", "nnr_density_pass_f16.inc"]
-    assert "nnr_bricks_f16.hip" in b.DENSITY_UNITS
-    own = b.own_headers("nnr_bricks_f16.hip")
-    assert all(h in own for h in shared) and all(h in own for h in b.SPLIT2_ONLY)
-    assert "nnr_resample_row.h" not in own and "nnr_wgrad_plan.h" not in own
-    with open(os.path.join(csrc, "nnr_bricks_f16.hip")) as f:
-        lines = [l.strip() for l in f]
-    for h in shared:
-        assert lines.count('#include "%s"' % h) == 1, h
-    assert '#include "nnr_trunk_f16.inc"' not in lines           # the trunk's text comes through the pass alone
-    # the point is formed without contraction, as the grid kernel forms it
-    assert "#pragma clang fp contract(off)" in lines
-    # the geometry header makes the host unit that includes it stale, and no kernel
-    geo = [h for h in b.own_headers("nnr_api.cpp") if h.endswith("nnr_geometry.h")]
-    assert len(geo) == 1 and os.path.samefile(os.path.join(csrc, geo[0]), os.path.join(ROOT, "include", "nnr_geometry.h"))
-    assert not any(h.endswith("nnr_geometry.h") for src, _ in b.SOURCES if src != "nnr_api.cpp" for h in b.own_headers(src))

@@ -1,6 +1,6 @@
 """CPU: the depth-fusion side of the geometry export without a GPU -- where the two entry points are declared and listed,
-every error return of both reached with fake device pointers before anything is dereferenced or launched, the wrappers' refusal of CPU tensors,
-what the build script holds the two kernels to, and the host side of model/geometry.py (extract_mesh_tsdf, tsdf_select_cells) on the reference
+every error return of both reached with fake device pointers before anything is dereferenced or launched, the wrappers' refusal of CPU tensors
+(what the build script holds the two kernels to: test_build_cpu.py), and the host side of model/geometry.py (extract_mesh_tsdf, tsdf_select_cells) on the reference
 integrator of tests/fusion_ref.py: an analytic sphere seen from 14 cameras."""
 import ctypes as C
 import functools
@@ -195,58 +195,6 @@ def test_the_gpu_only_geometry_functions_say_so_on_the_cpu():
     ndc = mdl.Renderer(_net(), dict(cfg, sample_option='ndc'), device=torch.device('cpu'))
     with pytest.raises(NotImplementedError, match="NDC"):
         G.render_depth_maps(ndc, K, Wm, (4, 4))
-
-
-# ------------------------------------------------------------------------------------------------------------ the build script
-def _build_module():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("nnr_build", os.path.join(ROOT, "nope-nerf_amd", "csrc", "build.py"))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    return b
-
-
-def test_the_build_holds_both_kernels_to_no_scratch():
-    b = _build_module()
-    assert b.SCRATCH_LIMIT["16depth_f16_kernelI"] == 0 and b.SCRATCH_LIMIT["21tsdf_integrate_kernelE"] == 0
-    for src in ("nnr_depth_f16.hip", "nnr_tsdf.hip", "nnr_fusion_api.cpp"):
-        assert (src, ()) in b.SOURCES
-    for remark in ("remark: Function Name: _ZN3nnr16depth_f16_kernelILi256EEEvNS_9DepthArgsE\nremark:     ScratchSize [bytes/lane]: %d\n",
-                   "remark: Function Name: _ZN3nnr16depth_f16_kernelILi128EEEvNS_9DepthArgsE\nremark:     ScratchSize [bytes/lane]: %d\n",
-                   "remark: Function Name: _ZN3nnr21tsdf_integrate_kernelENS_8TsdfArgsE\nremark:     ScratchSize [bytes/lane]: %d\n"):
-        b.check_resources(remark % 0, "fusion")
-        with pytest.raises(RuntimeError, match="scratch"):
-            b.check_resources(remark % 16, "fusion")
-
-
-def test_the_build_rebuilds_the_depth_unit_for_the_shared_pass_and_keeps_the_headers_apart():
-    b = _build_module()
-    csrc = os.path.join(ROOT, "nope-nerf_amd", "csrc")
-    shared = ["nnr_density_setup_f16.inc", "nnr_density_pass_f16.inc"]
-    assert "nnr_depth_f16.hip" in b.DENSITY_UNITS and "nnr_tsdf.hip" not in b.DENSITY_UNITS
-    own = b.own_headers("nnr_depth_f16.hip")
-    assert all(h in own for h in shared) and all(h in own for h in b.SPLIT2_ONLY) and "nnr_fusion_kernels.h" in own
-    for src in ("nnr_depth_f16.hip", "nnr_tsdf.hip", "nnr_fusion_api.cpp"):
-        own = b.own_headers(src)
-        assert "nnr_resample_row.h" not in own and "nnr_wgrad_plan.h" not in own and "nnr_fusion_kernels.h" in own, src
-        assert all(os.path.exists(os.path.join(csrc, h)) for h in own), src
-        text = open(os.path.join(csrc, src)).read()
-        assert '#include "nnr_resample_row.h"' not in text and '#include "nnr_wgrad_plan.h"' not in text, src
-        assert "atomic" not in re.sub(r"//.*", "", text), src
-    with open(os.path.join(csrc, "nnr_depth_f16.hip")) as f:
-        lines = [l.strip() for l in f]
-    for h in shared:
-        assert lines.count('#include "%s"' % h) == 1, h
-    assert '#include "nnr_trunk_f16.inc"' not in lines
-    with open(os.path.join(csrc, "nnr_tsdf.hip")) as f:
-        assert "#pragma clang fp contract(off)" in [l.strip() for l in f]
-    # the public header makes its host unit stale and nothing else; the internal one the three fusion units
-    fus = [h for h in b.own_headers("nnr_fusion_api.cpp") if h.endswith("nnr_fusion.h")]
-    assert len(fus) == 1 and os.path.samefile(os.path.join(csrc, fus[0]), os.path.join(ROOT, "include", "nnr_fusion.h"))
-    for src in sorted({s for s, _ in b.SOURCES}):
-        own = b.own_headers(src)
-        assert any(h.endswith("nnr_fusion.h") for h in own) == (src == "nnr_fusion_api.cpp"), src
-        assert ("nnr_fusion_kernels.h" in own) == (src in ("nnr_depth_f16.hip", "nnr_tsdf.hip", "nnr_fusion_api.cpp")), src
 
 
 # ------------------------------------------------------------------------------------------------------------ the reference alone: a sphere

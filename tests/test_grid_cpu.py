@@ -113,48 +113,3 @@ def test_ops_density_grid_raises_on_cpu_weights():
                                   'rendering': {'white_background': False, 'dist_alpha': False}})
     with pytest.raises(RuntimeError):
         ops.density_grid((0., 0., 0.), (.1, .1, .1), (4, 4, 4), net.weights(), net.biases(), hidden=128)
-
-
-def test_the_build_holds_the_grid_kernel_to_no_scratch():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("nnr_build", os.path.join(ROOT, "nope-nerf_amd", "csrc", "build.py"))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    assert b.SCRATCH_LIMIT["15grid_f16_kernelI"] == 0 and ("nnr_grid_f16.hip", ()) in b.SOURCES
-    remark = "remark: Function Name: _ZN3nnr15grid_f16_kernelILi256EEEvNS_8GridArgsE\nremark:     ScratchSize [bytes/lane]: %d\n"
-    b.check_resources(remark % 0, "grid")
-    with pytest.raises(RuntimeError, match="scratch"):
-        b.check_resources(remark % 16, "grid")
-
-
-def test_the_build_rebuilds_the_density_units_for_the_shared_pass_only():
-    import importlib.util
-    csrc = os.path.join(ROOT, "nope-nerf_amd", "csrc")
-    spec = importlib.util.spec_from_file_location("nnr_build", os.path.join(csrc, "build.py"))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    shared = ["nnr_density_setup_f16.inc", "nnr_density_pass_f16.inc"]
-    density = ["nnr_march_f16.hip", "nnr_propose_f16.hip", "nnr_grid_f16.hip"]
-    assert sorted(b.DENSITY_ONLY) == sorted(shared)
-    for src in density:
-        own = b.own_headers(src)
-        assert all(h in own for h in shared) and all(h in own for h in b.SPLIT2_ONLY), src
-        assert os.path.exists(os.path.join(csrc, src)) and (src, ()) in b.SOURCES
-    for src in ("nnr_mlp_fwd_f16.hip", "nnr_mlp_dgrad_f16.hip"):
-        own = b.own_headers(src)
-        assert not any(h in own for h in shared) and all(h in own for h in b.SPLIT2_ONLY), src
-    for src in sorted({s for s, _ in b.SOURCES}):
-        assert ("nnr_resample_row.h" in b.own_headers(src)) == (src in ("nnr_resample.hip", "nnr_propose_f16.hip")), src
-        assert all(os.path.exists(os.path.join(csrc, h)) for h in b.own_headers(src)), src
-        # the host planners' header belongs to the two host units alone, and is no common header: touching it rebuilds no kernel
-        assert ("nnr_wgrad_plan.h" in b.own_headers(src)) == (src in ("nnr_api.cpp", "nnr_wgrad_plan.cpp")), src
-    assert ("nnr_wgrad_plan.cpp", ()) in b.SOURCES and "nnr_wgrad_plan.h" not in b.HEADERS
-    # the three kernels include both shared files, and the trunk's text through the pass alone
-    for src in density:
-        with open(os.path.join(csrc, src)) as f:
-            lines = [l.strip() for l in f]
-        for h in shared:
-            assert lines.count('#include "%s"' % h) == 1, (src, h)
-        assert '#include "nnr_trunk_f16.inc"' not in lines, src
-    with open(os.path.join(csrc, "nnr_density_pass_f16.inc")) as f:
-        assert [l.strip() for l in f].count('#include "nnr_trunk_f16.inc"') == 1

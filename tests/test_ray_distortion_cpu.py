@@ -1,6 +1,6 @@
 """CPU: the ray-distortion regulariser without a GPU -- where its two entry points are declared and listed, every error
-return reached with fake device pointers and host-side outputs that must stay untouched, the wrappers' refusal of CPU tensors, the build's
-scratch entries, and the float64 reference of tests/ray_distortion_ref.py against itself: the O(N) prefix form is the pairwise definition and
+return reached with fake device pointers and host-side outputs that must stay untouched, the wrappers' refusal of CPU tensors
+(the build's scratch entries: test_build_cpu.py), and the float64 reference of tests/ray_distortion_ref.py against itself: the O(N) prefix form is the pairwise definition and
 the closed-form gradient the backward kernel evaluates is autograd's."""
 import ctypes as C
 import os
@@ -48,24 +48,6 @@ def test_the_entry_points_live_in_the_regularise_header_under_abi_8():
     for name, params in protos.items():
         assert len(getattr(lib, name).argtypes) == params.count(",") + 1, name
     assert len(lib.nnr_ray_distortion_fwd.argtypes) == 8 and len(lib.nnr_ray_distortion_bwd.argtypes) == 11
-
-
-def test_the_build_holds_both_kernels_to_no_scratch():
-    sys.path.insert(0, os.path.join(ROOT, "nope-nerf_amd", "csrc"))
-    import build as B
-    assert B.SCRATCH_LIMIT["25ray_distortion_fwd_kernelE"] == 0 and B.SCRATCH_LIMIT["25ray_distortion_bwd_kernelE"] == 0
-    names = [s for s, _ in B.SOURCES]
-    assert "nnr_ray_distortion.hip" in names and "nnr_regularise_api.cpp" in names
-    for unit in ("nnr_ray_distortion.hip", "nnr_regularise_api.cpp"):
-        assert "nnr_regularise_kernels.h" in B.own_headers(unit)
-        assert any(h.endswith("nnr_regularise.h") for h in B.own_headers(unit))
-    assert "nnr_regularise_kernels.h" not in B.own_headers("nnr_composite.hip") + B.own_headers("nnr_api.cpp") + B.HEADERS
-    # a remark of either kernel with scratch fails the build's check; one without passes
-    remark = "remark: Function Name: _ZN3nnr25ray_distortion_%s_kernelENS_17RayDistortionArgsE\nremark:     ScratchSize [bytes/lane]: %d\n"
-    for k in ("fwd", "bwd"):
-        B.check_resources(remark % (k, 0), "test")
-        with pytest.raises(RuntimeError):
-            B.check_resources(remark % (k, 8), "test")
 
 
 # ------------------------------------------------------------------------------------------------------------ error returns

@@ -152,20 +152,6 @@ def test_the_wrapper_refuses_cpu_tensors():
         ops.render_sparse(t, t, t, torch.zeros(8), torch.ones(8), None, grid, [], [], hidden=128, dist_alpha=False, white_bg=False, relu_sigma=False)
 
 
-def test_the_build_script_holds_the_kernel_to_the_inference_forwards_scratch():
-    sys.path.insert(0, os.path.join(ROOT, "nope-nerf_amd", "csrc"))
-    import build as B
-    assert ("nnr_sparse_f16.hip", ()) in B.SOURCES and ("nnr_sparse_api.cpp", ()) in B.SOURCES
-    assert B.SCRATCH_LIMIT["17sparse_f16_kernelI"] <= B.SCRATCH_LIMIT["18mlp_fwd_f16_kernelILi256ELb0E"]
-    own = B.own_headers("nnr_sparse_f16.hip")
-    assert "nnr_sparse_kernels.h" in own and "nnr_trunk_f16.inc" in own and "nnr_sparse_kernels.h" in B.own_headers("nnr_sparse_api.cpp")
-    for src, _ in B.SOURCES:
-        if src not in ("nnr_sparse_f16.hip", "nnr_sparse_api.cpp"):
-            assert "nnr_sparse_kernels.h" not in B.own_headers(src), src
-    with pytest.raises(RuntimeError):
-        B.check_resources("Function Name: _ZN3nnr17sparse_f16_kernelILi256EEEvNS_10SparseArgsE\nScratchSize [bytes/lane]: 64\n", "x")
-
-
 # ------------------------------------------------------------------------------------------------------------ occupancy_bits
 def _bits_by_loops(vol, level, dilate):
     v = vol.numpy()
