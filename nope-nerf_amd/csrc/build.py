@@ -17,6 +17,9 @@ LIB = os.path.join(os.path.dirname(HERE), "nnr", "libnnr.so")
 SOURCES = [("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MODE=2")), ("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=0", "NNR_FWD_MODE=2")),
            ("nnr_wgrad.hip", ()), ("nnr_wgrad.hip", ("NNR_WGRAD_F16_TU=1",)), ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=256",)),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=0")),
+           # the frozen-field variants (include/nnr_frozen.h): the training forward and the input gradient without their stashes, one unit per D
+           ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=2")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_STASH=0")),
+           ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=2")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=128", "NNR_DGRAD_STASH=0")),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=128",)),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_sparse_f16.hip", ()), ("nnr_march_f16.hip", ()), ("nnr_propose_f16.hip", ()), ("nnr_grid_f16.hip", ()), ("nnr_bricks_f16.hip", ()),
            ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_MODE=2")),
@@ -47,6 +50,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-prag
 # prologue values in scratch, reloaded at pass start (where the pass waits for its inputs anyway), nothing inside a pass; the inference forward (no stores in flight) may spill its composite carry.
 # (three-term kernels: only the D = 256 training forward keeps a few pass-start values in scratch, 32 bytes)
 SCRATCH_LIMIT = {"18mlp_fwd_f16_kernelI": 0, "18mlp_fwd_f16_kernelILi256ELb0E": 48, "18mlp_fwd_f16_kernelILi128ELb0E": 48,      # (inference: prologue values and the composite carry, outside the MFMA streams)
+                 "25mlp_fwd_frozen_f16_kernelI": 0,      # (the frozen-field forward; its input gradient is mlp_dgrad_f16_kernel<D, false>: the next key)
                  "20mlp_dgrad_f16_kernelI": 0, "14mlp_fwd_kernelI": 0, "14mlp_fwd_kernelILi256ELb1ELi2E": 48, "16mlp_dgrad_kernelI": 0, "12wgrad_kernelI": 0, "14wgrad_b_kernelE": 0,
                  "19mlp_fwd_bf16_kernelI": 48, "19mlp_fwd_bf16_kernelILi256ELb1E": 16, "19mlp_fwd_bf16_kernelILi128ELb1E": 16,
                  "21mlp_dgrad_bf16_kernelI": 64, "20composite_fwd_kernelE": 0, "20composite_bwd_kernelE": 0,
@@ -75,7 +79,26 @@ def check_resources(remarks, what):
         raise RuntimeError("%s: a hot kernel uses scratch memory -- a loop did not unroll or registers spilled:\n  " % what + "\n  ".join(bad))
 
 
-WORKERS = max(2, min(12, (os.cpu_count() or 4)))
+def _usable_cpus():
+    """CPUs this process may really use: os.cpu_count() is the whole machine's, while an affinity mask, a cgroup quota or MAX_JOBS may allow
+    fewer -- and more compile jobs than CPUs only stretch the two 20-minute units that decide how long a full build takes."""
+    n = os.cpu_count() or 4
+    if hasattr(os, "sched_getaffinity"):
+        n = min(n, len(os.sched_getaffinity(0)))
+    try:
+        with open("/sys/fs/cgroup/cpu.max") as f:      # cgroup v2: "<quota> <period>" in microseconds, or "max <period>"
+            quota, period = f.read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    jobs = os.environ.get("MAX_JOBS", "")
+    if jobs.isdigit() and int(jobs) > 0:
+        n = min(n, int(jobs))
+    return n
+
+
+WORKERS = max(2, min(12, _usable_cpus()))
 
 
 def _stale(target, deps):

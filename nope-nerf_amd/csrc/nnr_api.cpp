@@ -12,6 +12,7 @@
 #include "../../include/nnr.h"
 #include "../../include/nnr_geometry.h"
 #include "nnr_device.h"
+#include "nnr_frozen_kernels.h"
 #include "nnr_kernels.h"
 #include "nnr_layout.h"
 #include "nnr_wgrad_plan.h"
@@ -50,16 +51,6 @@ size_t packed_floats(int D, int mode) {
     return D == 256 ? (size_t)Layout<256>::packed_floats : (size_t)Layout<128>::packed_floats;
 }
 
-// Ray mode of the two MLP kernels (nnr_mlp_fwd.hip): a wave walks the N / 32 chunks of ONE ray, a workgroup four rays.  Needs whole
-// chunks per ray and whole workgroups; everything else runs the flat decomposition (same sample numbering, same planes).
-// The bf16 kernels (nnr_mlp_fwd_bf16.hip) work on PAIRS of chunks: their unit is 64 samples.
-int chunks_per_ray(const nnr_cfg* c) {
-    static const bool off = std::getenv("NNR_FLAT_GRID") != nullptr;    // experiments: force the flat decomposition
-    const int unit = is_bf16(c) ? kBf16Tiles * kChunk : kChunk;         // samples a wave takes per pass
-    const int waves = is_bf16(c) ? kBf16Waves : kWavesPerBlock;         // = rays per workgroup in ray mode
-    return (!off && c->n_samples % unit == 0 && c->n_rays % waves == 0) ? c->n_samples / unit : 0;
-}
-
 // the 12 gradient tensors of a weight-gradient launch ([12], the merged matrix's scratch, is the caller's); false: one is null
 template <class Args>
 bool fill_grads(const nnr_param_grads* g, Args& a) {
@@ -90,6 +81,17 @@ int launched(hipError_t e) {
     if (e == hipSuccess) return NNR_OK;
     g_last_hip = (int)e;
     return NNR_E_HIP;
+}
+
+// Ray mode of the two MLP kernels (nnr_mlp_fwd.hip): a wave walks the N / 32 chunks of ONE ray, a workgroup four rays.  Needs whole
+// chunks per ray and whole workgroups; everything else runs the flat decomposition (same sample numbering, same planes).
+// The bf16 kernels (nnr_mlp_fwd_bf16.hip) work on PAIRS of chunks: their unit is 64 samples.  Not file-local: the frozen-field entry
+// points (nnr_frozen_api.cpp) decompose their launches by the same rule.
+int chunks_per_ray(const nnr_cfg* c) {
+    static const bool off = std::getenv("NNR_FLAT_GRID") != nullptr;    // experiments: force the flat decomposition
+    const int unit = is_bf16(c) ? kBf16Tiles * kChunk : kChunk;         // samples a wave takes per pass
+    const int waves = is_bf16(c) ? kBf16Waves : kWavesPerBlock;         // = rays per workgroup in ray mode
+    return (!off && c->n_samples % unit == 0 && c->n_rays % waves == 0) ? c->n_samples / unit : 0;
 }
 }  // namespace nnr
 
@@ -753,3 +755,6 @@ int nnr_aux_terms_bwd(const nnr_aux_cfg* cfg, const float* d1_img, const float* 
 }
 
 }  // extern "C"
+
+// the frozen-field entry points (include/nnr_frozen.h), part of this unit: see the file's header
+#include "nnr_frozen_api.cpp"

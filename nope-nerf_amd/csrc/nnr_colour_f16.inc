@@ -21,11 +21,11 @@
         const float inv = inv_scale<L>(bias, 7);
         const char* const pl = xh(7);
         // (stash stores: every second unit one octet; gemm_part2's PRE: those the trunk's last pass certainly issued while it consumed its last panel)
-        gemm_part2<DT, HT, NP, 1, 0, TRAIN ? 2 : 0, TRAIN ? mode_gp(HT, 3) : 0>(accA, ph, pm, pipe, p0(F_RGBH_F),
+        gemm_part2<DT, HT, NP, 1, 0, NNR_STASH_ACT ? 2 : 0, NNR_STASH_ACT ? mode_gp(HT, 3) : 0>(accA, ph, pm, pipe, p0(F_RGBH_F),
                                                                              NNR_FINISH(accB, NP, mwB, inv, pl, HR / 4, true));
     }
     if constexpr (TRAIN) store_mask<L>(st.mask_base, mwB, 7, 1);
-    flush_max<TRAIN>(st, 7, lane, mx, mxa);
+    flush_max<TRAIN, NNR_STASH_ACT>(st, 7, lane, mx, mxa);
     const float sg = sg0 + sg1;
     const float sigma_raw = sg + __shfl_xor(sg, 32, 64) + bias[L::bias_off(8)];
     {
@@ -50,7 +50,7 @@
         }
     }
     if constexpr (TRAIN) store_mask<L>(st.mask_base, mwA, 8, 0);
-    if constexpr (TRAIN) {      // registers 4 q .. 4 q + 3 = features 8 q + 4 half + {0..3}: octet q of the plane, one whole block per store
+    if constexpr (NNR_STASH_ACT) {      // registers 4 q .. 4 q + 3 = features 8 q + 4 half + {0..3}: octet q of the plane, one whole block per store
         const char* const pg = xg();
 #pragma unroll
         for (int q = 0; q < HR / 4; ++q) tile_store(pg, lane_off, q, f32x4{g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]});

@@ -14,7 +14,12 @@
 //   * between the layers a lane holds the packed terms of the scaled gradient, made once by the epilogue unit that finishes a pair:
 //     accumulator pair -> ReLU' (AND with the gate bits) -> 1 / s_w of the weights just applied -> [1 / s -> every second unit one whole-block
 //     non-temporal store to the gradient plane] -> split.
+// STASH = false (csrc/build.py: NNR_DGRAD_STASH=0) is the FROZEN-FIELD build: the same chain down to d(point), d(view dir) with nothing left
+// for a weight gradient -- no store to P_DH1..8 / P_DG, no zeroing of the padded rows of P_DOUT4, no plane maxima.  The per-sample scale and
+// recentre() live in registers and are what they are in the stashing build, so the two builds' outputs are equal bit for bit.  ws_dh, ws_dg and
+// plane_max are null in its argument block (nnr_frozen_api.cpp): every store through them is compiled out, none is guarded at run time.
 #include "nnr_device.h"
+#include "nnr_frozen_kernels.h"
 #include "nnr_kernels.h"
 #include "nnr_split2.h"
 
@@ -72,7 +77,7 @@ __device__ __forceinline__ f32x4 enc_backward(const G& g, const float (&pv)[NR],
 }
 }  // namespace f16dg
 
-template <int D>
+template <int D, bool STASH>
 __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
     using L = Layout<D, 3>;
     using Pipe = Split2PipeT<false>;
@@ -83,7 +88,8 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
     constexpr int HW = (HR + 31) / 32;       // mask words per half
     constexpr int PP = mode_panels(DT, HT, 3);  // panels of one D x D/2 pass
     // stash stores a dense pass certainly issues while it consumes its last panel (gemm_part2's PRE of the part behind it): an "ahead" pass one per row but the last, a "behind" pass one per row
-    constexpr int kPreA = mode_gp(HT, 3) - 1, kPreB = mode_gp(HT, 3);
+    constexpr int kPreA = STASH ? mode_gp(HT, 3) - 1 : 0, kPreB = STASH ? mode_gp(HT, 3) : 0;
+    constexpr int SE = STASH ? 2 : 0;      // every second unit stores an octet
     const int lane0 = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
 
@@ -95,7 +101,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
     float* const ltab = reinterpret_cast<float*>(smem + kRingF4 + kPark);
     for (int i = threadIdx.x; i < kTab; i += 256) ltab[i] = a.packed[L::head_base + i];
     __shared__ uint32_t wg_max[9];      // the workgroup's largest |gradient| per plane P_DH1..8 ([0..8)) and P_DG ([8]), as integers
-    if (threadIdx.x < 9) wg_max[threadIdx.x] = 0;
+    if (STASH && threadIdx.x < 9) wg_max[threadIdx.x] = 0;
     __syncthreads();   // before any DMA is in flight: the only full barrier in front of the passes
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     Pipe pipe{reinterpret_cast<const f32x4*>(a.packed + L::bwd_base) + wave_u * (Pipe::PW * 64), smem, wave_u, lane0, L::bwd_panels};
@@ -124,7 +130,9 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
 
     f32x4 dout = {0.f, 0.f, 0.f, 0.f};
     if (live) dout = *reinterpret_cast<const f32x4*>(a.ws_dout4 + 4 * s);
-    else if (half == 0) *reinterpret_cast<f32x4*>(a.ws_dout4 + 4 * s) = dout;   // padded rows feed the weight-gradient kernel: zero them
+    else if constexpr (STASH) {
+        if (half == 0) *reinterpret_cast<f32x4*>(a.ws_dout4 + 4 * s) = dout;   // padded rows feed the weight-gradient kernel: zero them
+    }
 
     uint32_t ph[8 * DT], pm[8 * DT];      // packed terms of the current D-wide SCALED gradient (pairs [0, NP): half A, [NP, 2 NP): half B), rewritten in place
     f32x16 accA[HT], accB[HT];           // halves A ([0,D/2)) and B ([D/2,D)) of the gradient being computed
@@ -139,8 +147,10 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
     // The packed terms of this plane stay as they are (scale sS_old); the accumulators made from them carry sS_old, and the units that finish the
     // next plane multiply by cW = sS_new / sS_old on the way (exact: a power of two) and stash with 1 / sS_new.
     auto flush_max = [&](int plane, bool recentre = true) __attribute__((always_inline)) {
-        const float m = wave_max_f32(mxd);
-        if (lane == 0) atomicMax(&wg_max[plane], __float_as_uint(m));
+        if constexpr (STASH) {
+            const float m = wave_max_f32(mxd);
+            if (lane == 0) atomicMax(&wg_max[plane], __float_as_uint(m));
+        }
         if (recentre) {
             const float sm = fmaxf(mxd, __shfl_xor(mxd, 32, 64)) * sS;                      // the sample's largest scaled magnitude in this plane
             const int eb = (int)((__float_as_uint(sm) >> 23) & 255u);
@@ -180,9 +190,11 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
             }
         }
         // d g goes to P_DG: block (chunk, octet q) + 16 bytes per lane
-        const char* const dgp = reinterpret_cast<const char*>(a.ws_dg + chunk * (int64_t)((D / 16) * 256));
+        if constexpr (STASH) {
+            const char* const dgp = reinterpret_cast<const char*>(a.ws_dg + chunk * (int64_t)((D / 16) * 256));
 #pragma unroll
-        for (int q = 0; q < HR / 4; ++q) tile_store(dgp, lane_off, q, f32x4{dg[4 * q], dg[4 * q + 1], dg[4 * q + 2], dg[4 * q + 3]});
+            for (int q = 0; q < HR / 4; ++q) tile_store(dgp, lane_off, q, f32x4{dg[4 * q], dg[4 * q + 1], dg[4 * q + 2], dg[4 * q + 3]});
+        }
         // the sample's scale: the largest magnitude that enters its chain -- its d g (both half-waves) and the density head's rank-1 term --
         // to [2^7, 2^8); a power of two from the exponent field, clamped to 2^+-100; 1 for an all-zero sample
         mxd = mx;
@@ -220,11 +232,14 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
         const int r = 2 * u;                                                                                     \
         float t0, t1;                                                                                            \
         f16dg::sel_unit(ACC[r >> 4][r & 15], ACC[(r + 1) >> 4][(r + 1) & 15], MW[r >> 5], INV, sInv, t0, t1, ph[(OFFP) + u], pm[(OFFP) + u], r & 31, mxd); \
-        if (u & 1) tile_store(PLANE, lane_off, (BLK0) + (u >> 1), f32x4{keep[0], keep[1], t0, t1});              \
-        else keep = f32x2{t0, t1};                                                                               \
+        if constexpr (STASH) {                                                                                   \
+            if (u & 1) tile_store(PLANE, lane_off, (BLK0) + (u >> 1), f32x4{keep[0], keep[1], t0, t1});          \
+            else keep = f32x2{t0, t1};                                                                           \
+        }                                                                                                        \
     }
     auto dh = [&](int hidden_idx /*0..7*/) -> const char* {      // block (this chunk, octet 0) of the gradient plane of hidden layer hidden_idx + 1
-        return reinterpret_cast<const char*>(a.ws_dh + (int64_t)hidden_idx * a.S_pad * D + chunk * (int64_t)((D / 8) * 256));
+        if constexpr (!STASH) return nullptr;
+        else return reinterpret_cast<const char*>(a.ws_dh + (int64_t)hidden_idx * a.S_pad * D + chunk * (int64_t)((D / 8) * 256));
     };
     auto inv_scale = [&](int slot) __attribute__((always_inline)) { return uniform(lscale[16 + slot]); };
 
@@ -236,7 +251,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
     {
         const float inv = inv_scale(8) * cW;      // (per lane: the plane's re-centring factor rides on 1 / s_w)
         const char* const pl = dh(7);
-        gemm_part2<HT, HT, NP, 0, 4, 2, 0>(accB, gh, gm, pipe, p0(B_RGBH_FB), NNR_SELECT(accA, 0, mwA, inv, pl, 0));
+        gemm_part2<HT, HT, NP, 0, 4, SE, 0>(accB, gh, gm, pipe, p0(B_RGBH_FB), NNR_SELECT(accA, 0, mwA, inv, pl, 0));
     }
     {
         float pvd[16];   // stored direction encoding (sin<->cos partners): the loads land under this short pass
@@ -263,7 +278,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
         {   // pass A: its first half of rows only reads pairs [0, NP); the previous gradient's half B is finished meanwhile
             const float inv = inv_scale(k + 1) * cW;
             const char* const pl = dh(k);
-            gemm_part2<DT, HT, NP, 1, 0, 2, kPreB>(accA, ph, pm, pipe, pa, NNR_SELECT(accB, NP, mwB, inv, pl, HR / 4), pre);
+            gemm_part2<DT, HT, NP, 1, 0, SE, kPreB>(accA, ph, pm, pipe, pa, NNR_SELECT(accB, NP, mwB, inv, pl, HR / 4), pre);
         }
         flush_max(k);      // the gradient of hidden k + 1 (plane P_DH1 + k) is complete
         load_mask(mwB, k - 1, 1);
@@ -271,7 +286,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
         {   // pass B: half A of the new gradient replaces pairs [0, NP) in place, one row behind the reads
             const float inv = inv_scale(k) * cW;
             const char* const pl = dh(k - 1);
-            gemm_part2<DT, HT, NP, 2, 0, 2, kPreA>(accB, ph, pm, pipe, pa + PP, NNR_SELECT(accA, 0, mwA, inv, pl, 0));
+            gemm_part2<DT, HT, NP, 2, 0, SE, kPreA>(accB, ph, pm, pipe, pa + PP, NNR_SELECT(accA, 0, mwA, inv, pl, 0));
         }
     };
     // hidden 8,7,6 -> d pre-activation of 7,6,5
@@ -286,7 +301,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
         {
             const float inv = inv_scale(5) * cW;
             const char* const pl = dh(4);
-            gemm_part2<DT, 2, NP, 1, 0, 2, kPreB>(acce, ph, pm, pipe, p0(B_L5E), NNR_SELECT(accB, NP, mwB, inv, pl, HR / 4));
+            gemm_part2<DT, 2, NP, 1, 0, SE, kPreB>(acce, ph, pm, pipe, p0(B_L5E), NNR_SELECT(accB, NP, mwB, inv, pl, HR / 4));
         }
         sInv4 = sInv;      // (the encoding rows of the skip layer were multiplied into plane 4's terms: their scale, before it is re-centred)
         flush_max(4);
@@ -302,7 +317,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
     {
         const float inv = inv_scale(4) * cW;
         const char* const pl = dh(3);
-        gemm_part2<DT, HT, NP, 2, 0, 2, 0>(accB, ph, pm, pipe, p0(B_L5HB), NNR_SELECT(accA, 0, mwA, inv, pl, 0));
+        gemm_part2<DT, HT, NP, 2, 0, SE, 0>(accB, ph, pm, pipe, p0(B_L5HB), NNR_SELECT(accA, 0, mwA, inv, pl, 0));
     }
     // hidden 4,3,2 -> d pre-activation of 3,2,1
 #pragma unroll 1
@@ -319,7 +334,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
         {
             const float inv = inv_scale(1) * cW;
             const char* const pl = dh(0);
-            gemm_part2<DT, 2, NP, 1, 0, 2, kPreB>(acc2, ph, pm, pipe, p0(B_L1), NNR_SELECT(accB, NP, mwB, inv, pl, HR / 4));
+            gemm_part2<DT, 2, NP, 1, 0, SE, kPreB>(acc2, ph, pm, pipe, p0(B_L1), NNR_SELECT(accB, NP, mwB, inv, pl, HR / 4));
         }
         flush_max(0, false);      // (the last plane: the scale of its terms is what acc2 carries)
         const float c1 = inv_scale(0) * sInv, c4 = inv_scale(4) * sInv4;      // out of the accumulators' units: weights of slot 0 / slot 4, the scale of the terms each was made from
@@ -336,17 +351,26 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
 #undef NNR_SELECT
     pipe.next_pass(pass + 2 < n_pass);
     }   // pass
+    if constexpr (STASH) {
     __syncthreads();      // the workgroup's maxima to the launch's table (the weight-gradient kernel's scales): P_DH1..8 at [8, 16), P_DG at [16]
     if (a.plane_max != nullptr && threadIdx.x < 9) atomicMax(reinterpret_cast<uint32_t*>(a.plane_max) + 8 + threadIdx.x, wg_max[threadIdx.x]);
+    }
 }
 
-// one D per translation unit (csrc/build.py: -DNNR_DGRAD_D=..), as for nnr_mlp_dgrad.hip
-#ifdef NNR_DGRAD_D
+// one (D, STASH) per translation unit (csrc/build.py: -DNNR_DGRAD_D=.. [-DNNR_DGRAD_STASH=0]), as for nnr_mlp_dgrad.hip
+#if defined(NNR_DGRAD_D) && defined(NNR_DGRAD_STASH) && NNR_DGRAD_STASH == 0
+template <>
+hipError_t launch_mlp_dgrad_frozen_variant<NNR_DGRAD_D>(const MlpDgradArgs& a, hipStream_t st) {
+    dim3 grid((unsigned)(a.chunks_per_ray > 0 ? a.S_pad / kBlockSamples / a.chunks_per_ray : a.S_pad / kBlockSamples)), block(256);
+    hipLaunchKernelGGL((mlp_dgrad_f16_kernel<NNR_DGRAD_D, false>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+#elif defined(NNR_DGRAD_D)
 template <>
 hipError_t launch_mlp_dgrad_variant<NNR_DGRAD_D, 3>(const MlpDgradArgs& a, hipStream_t st) {
     dim3 grid((unsigned)(a.chunks_per_ray > 0 ? a.S_pad / kBlockSamples / a.chunks_per_ray : a.S_pad / kBlockSamples)), block(256);
     prof_before(PROF_DGRAD, st);
-    hipLaunchKernelGGL((mlp_dgrad_f16_kernel<NNR_DGRAD_D>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((mlp_dgrad_f16_kernel<NNR_DGRAD_D, true>), grid, block, 0, st, a);
     prof_after(PROF_DGRAD, st);
     return hipGetLastError();
 }

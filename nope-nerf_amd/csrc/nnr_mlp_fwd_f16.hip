@@ -6,14 +6,27 @@
 // (nnr_trunk_f16.h, which says what differs from the six-term kernel; the occupancy march, nnr_march_f16.hip, shares it), the colour branch
 // (nnr_colour_f16.inc, shared with the sparse render nnr_sparse_f16.hip) and the output.  The density head is summed inside the units of hidden 8 (the fp32 values exist only there).
 // Roofline: the matrix pipe in fp16 (2.5 PFLOP/s dense): 3 x 528 000 MACs per sample executed.
+// A third build beside inference and training (csrc/build.py: NNR_FWD_TRAIN=2), the FROZEN-FIELD forward mlp_fwd_frozen_f16_kernel: the
+// training forward for a step that wants the ray gradients only.  It leaves what the input-gradient kernel reads -- the gate words, the two
+// encoding planes, z and the outputs -- keeps the range guard, and neither stores the hidden and colour-hidden activations nor keeps the
+// plane maxima: both exist for the weight gradient alone.  Its argument block carries null pointers for those planes (nnr_frozen_api.cpp);
+// every store through them is compiled out (NNR_STASH_ACT, nnr_trunk_f16.h), none is guarded at run time.
+#if defined(NNR_FWD_TRAIN) && NNR_FWD_TRAIN == 2
+#define NNR_STASH_ACT false
+#define NNR_FWD_KERNEL mlp_fwd_frozen_f16_kernel
+#else
+#define NNR_FWD_KERNEL mlp_fwd_f16_kernel
+#endif
 #include "nnr_trunk_f16.h"
+#include "nnr_frozen_kernels.h"
 
 namespace nnr {
 
 static_assert(kTileActPlanes, "the activation planes of a three-term / two-term training workspace are tile-major");
 
 template <int D, bool TRAIN>
-__global__ __launch_bounds__(256, 1) void mlp_fwd_f16_kernel(MlpFwdArgs a) {
+__global__ __launch_bounds__(256, 1) void NNR_FWD_KERNEL(MlpFwdArgs a) {
+    constexpr bool STASH = NNR_STASH_ACT;      // the kernel stores the activation planes and keeps their maxima
     using L = Layout<D, 3>;
     using Pipe = Split2PipeT<false>;
     constexpr int kRingF4 = kNBuf * Pipe::F4;
@@ -26,7 +39,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_f16_kernel(MlpFwdArgs a) {
     float* const ltab = reinterpret_cast<float*>(smem + kRingF4 + kPark);
     for (int i = threadIdx.x; i < L::table_floats; i += 256) ltab[i] = a.packed[L::bias_base + i];
     __shared__ uint32_t wg_max[9];      // training: the workgroup's largest stashed value per activation plane P_XH1..8 (as integers: the values are >= 0); [8]: the position encoding's
-    if (TRAIN && threadIdx.x < 9) wg_max[threadIdx.x] = 0;
+    if (STASH && threadIdx.x < 9) wg_max[threadIdx.x] = 0;
     __syncthreads();   // before any DMA is in flight: the only full barrier in front of the passes
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     Pipe pipe{reinterpret_cast<const f32x4*>(a.packed) + wave_u * (Pipe::PW * 64), smem, wave_u, lane0, L::fwd_panels};
@@ -78,6 +91,8 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_f16_kernel(MlpFwdArgs a) {
             const char* const xe = reinterpret_cast<const char*>(a.ws_xe + chunk_id * (int64_t)((kPosPad / 8) * 256));
 #pragma unroll
             for (int q = 0; q < 8; ++q) tile_store(xe, lane_off, q, f32x4{e[4 * q], e[4 * q + 1], e[4 * q + 2], e[4 * q + 3]});
+        }
+        if constexpr (STASH) {
             // the plane's largest magnitude (the weight gradient's two-term job against this plane scales by it: nnr_wgrad.hip wgrad_job_enc2): the
             // identity block's coordinates, or 1 (the sines and cosines)
             const float me = wave_max_f32(fmaxf(1.f, fmaxf(fabsf(px), fmaxf(fabsf(py), fabsf(pz)))));
@@ -111,7 +126,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_f16_kernel(MlpFwdArgs a) {
     float mxa = 0.f;                     // training: ... of all planes of this pass so far
     float sg0 = 0.f, sg1 = 0.f;          // density head: this lane's share of w_sigma . h8
     auto xh = [&](int hidden_idx /*0..7*/) -> const char* {      // block (this chunk, octet 0) of hidden layer hidden_idx + 1's activation plane
-        if constexpr (!TRAIN) return nullptr;
+        if constexpr (!STASH) return nullptr;
         else return reinterpret_cast<const char*>(a.ws_xh + (int64_t)hidden_idx * a.S_pad * D + chunk_id * (int64_t)((D / 8) * 256));
     };
 
@@ -122,7 +137,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_f16_kernel(MlpFwdArgs a) {
     }
 
     auto xg = [&]() -> const char* {      // block (this chunk, octet 0) of the colour-hidden activation plane
-        if constexpr (!TRAIN) return nullptr;
+        if constexpr (!STASH) return nullptr;
         else return reinterpret_cast<const char*>(a.ws_xg + chunk_id * (int64_t)((D / 16) * 256));
     };
 #include "nnr_colour_f16.inc"
@@ -172,7 +187,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_f16_kernel(MlpFwdArgs a) {
 #undef NNR_FINISH
     pipe.next_pass(pass + 2 < n_pass);
     }   // pass
-    if constexpr (TRAIN) {      // the workgroup's maxima to the launch's table (NNR_F_SPLIT2: the weight-gradient kernel's scales)
+    if constexpr (STASH) {      // the workgroup's maxima to the launch's table (NNR_F_SPLIT2: the weight-gradient kernel's scales)
         __syncthreads();
         if (a.plane_max != nullptr && threadIdx.x < 8) atomicMax(reinterpret_cast<uint32_t*>(a.plane_max) + threadIdx.x, wg_max[threadIdx.x]);
         if (a.plane_max != nullptr && threadIdx.x == 8) atomicMax(reinterpret_cast<uint32_t*>(a.plane_max) + 17, wg_max[8]);      // (kPlaneMaxEnc, nnr_wgrad.hip)
@@ -180,7 +195,14 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_f16_kernel(MlpFwdArgs a) {
 }
 
 // One (D, TRAIN) instantiation per translation unit (csrc/build.py: -DNNR_FWD_D=.. -DNNR_FWD_TRAIN=..), as for nnr_mlp_fwd.hip
-#ifdef NNR_FWD_D
+#if defined(NNR_FWD_D) && NNR_FWD_TRAIN == 2
+template <>
+hipError_t launch_mlp_fwd_frozen_variant<NNR_FWD_D>(const MlpFwdArgs& a, hipStream_t st) {
+    dim3 grid = mlp_fwd_grid(a), block(256);
+    hipLaunchKernelGGL((mlp_fwd_frozen_f16_kernel<NNR_FWD_D, true>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+#elif defined(NNR_FWD_D)
 template <>
 hipError_t launch_mlp_fwd_variant<NNR_FWD_D, (NNR_FWD_TRAIN != 0), 3>(const MlpFwdArgs& a, hipStream_t st) {
     dim3 grid = mlp_fwd_grid(a), block(256);

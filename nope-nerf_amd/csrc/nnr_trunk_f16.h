@@ -20,6 +20,13 @@
 
 #include <type_traits>
 
+// NNR_STASH_ACT: "this kernel stores activations" -- the hidden and colour-hidden planes (xh(i), xg()) and the plane maxima the weight
+// gradient scales by.  TRAIN unless the including unit says otherwise before this header: the frozen-field forward (nnr_mlp_fwd_f16.hip,
+// NNR_FWD_TRAIN=2) is a training forward -- gate words, encodings, the NaN guard's per-plane maxima -- that stores none of them.
+#ifndef NNR_STASH_ACT
+#define NNR_STASH_ACT TRAIN
+#endif
+
 namespace nnr {
 
 // One epilogue unit: pair u of a half (registers 2 u, 2 u + 1 of ACC) -> pair OFFP + u of the packed input of the next layer.
@@ -27,15 +34,17 @@ namespace nnr {
 // SIG: hidden 8 -- add the pair's share of the density head (its row sits in the head tables in register order).
 // A macro: its arguments name accumulator and mask arrays by token.  Names it takes from the scope it is used in: TRAIN, L, DT, bias, half, lane_off,
 // ph, pm (the packed terms), keep (the first pair of an octet between its unit and the next one's store), mx, sg0, sg1.  Used by nnr_trunk_f16.inc and
-// by the one part behind the trunk that finishes hidden 8 under the colour GEMM (nnr_mlp_fwd_f16.hip).
+// by the one part behind the trunk that finishes hidden 8 under the colour GEMM (nnr_mlp_fwd_f16.hip).  NNR_STASH_ACT (above) removes the stores alone.
 #define NNR_FINISH(ACC, OFFP, MW, INV, PLANE, BLK0, SIG)                                                           \
     [&](int u) __attribute__((always_inline)) {                                                                  \
         const int r = 2 * u;                                                                                     \
         float x0, x1;                                                                                            \
         if constexpr (TRAIN) {      /* (x > 0) == (relu(x) != 0): two gate bits appended to the half's mask word (nnr_split2.h) */ \
             unit_fwd_train(ACC[r >> 4][r & 15], ACC[(r + 1) >> 4][(r + 1) & 15], INV, MW[r >> 5], x0, x1, ph[(OFFP) + u], pm[(OFFP) + u], mx); \
-            if (u & 1) tile_store(PLANE, lane_off, (BLK0) + (u >> 1), f32x4{keep[0], keep[1], x0, x1});          \
-            else keep = f32x2{x0, x1};                                                                           \
+            if constexpr (NNR_STASH_ACT) {                                                                       \
+                if (u & 1) tile_store(PLANE, lane_off, (BLK0) + (u >> 1), f32x4{keep[0], keep[1], x0, x1});      \
+                else keep = f32x2{x0, x1};                                                                       \
+            }                                                                                                    \
         } else {                                                                                                 \
             unit_fwd_infer(ACC[r >> 4][r & 15], ACC[(r + 1) >> 4][(r + 1) & 15], INV, x0, x1, ph[(OFFP) + u], pm[(OFFP) + u], mx); \
         }                                                                                                        \
@@ -66,11 +75,14 @@ struct TrunkStash {
 };
 
 // A plane is complete (half A in the pass B of its layer, half B in the pass A of the next): its maximum to the workgroup's table
-template <bool TRAIN>
+// (STASH: the kernel stores the plane; without it only the sample's own running maximum moves on, for the range guard)
+template <bool TRAIN, bool STASH = TRAIN>
 __device__ __forceinline__ void flush_max(const TrunkStash& st, int plane, int lane, float& mx, float& mxa) {
     if constexpr (TRAIN) {
-        const float m = wave_max_f32(mx);
-        if (lane == 0) atomicMax(&st.wg_max[plane], __float_as_uint(m));
+        if constexpr (STASH) {
+            const float m = wave_max_f32(mx);
+            if (lane == 0) atomicMax(&st.wg_max[plane], __float_as_uint(m));
+        }
         mxa = fmaxf(mxa, mx);
         mx = 0.f;
     }

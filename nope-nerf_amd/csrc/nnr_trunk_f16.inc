@@ -1,6 +1,6 @@
 // nnr_trunk_f16.inc -- hidden 1 to 8 on packed fp16 terms (nnr_trunk_f16.h), as a block of statements: `{` #include "nnr_trunk_f16.inc" `}` inside
 // the pass loop of a kernel, behind its opaque lane id.  Names it takes from that scope:
-//   D, TRAIN, L = Layout<D, 3>, DT, HT      the kernel's template arguments and tile counts
+//   D, TRAIN, L = Layout<D, 3>, DT, HT      the kernel's template arguments and tile counts (NNR_STASH_ACT, nnr_trunk_f16.h: TRAIN unless the unit defines it)
 //   pipe, p0(part)                           the weight stream and a part's first panel in it (L::fwd_panel0)
 //   bias, lane, half                         the LDS tables (index with L::bias_off(layer), L::wsig_off, L::scale_off), the lane
 //   park                                     8 free 16-byte LDS slots of this lane (stride 64)
@@ -15,8 +15,8 @@
     constexpr int HW = (HR + 31) / 32;       // mask words per half
     constexpr int PP = mode_panels(DT, HT, 3);  // panels of one D x D/2 pass
     // stash stores a dense pass certainly issues while it consumes its last panel (gemm_part2's PRE of the part behind it): an "ahead" pass one per row but the last, a "behind" pass one per row
-    constexpr int kPreA = TRAIN ? mode_gp(HT, 3) - 1 : 0, kPreB = TRAIN ? mode_gp(HT, 3) : 0;
-    constexpr int SE = TRAIN ? 2 : 0;      // every second unit stores an octet
+    constexpr int kPreA = NNR_STASH_ACT ? mode_gp(HT, 3) - 1 : 0, kPreB = NNR_STASH_ACT ? mode_gp(HT, 3) : 0;
+    constexpr int SE = NNR_STASH_ACT ? 2 : 0;      // every second unit stores an octet
     const int lane_off = st.lane_off;
     uint32_t mwA[HW], mwB[HW];
     f32x2 keep = {0.f, 0.f};      // the first pair of an octet between its unit and the next one's store
@@ -55,7 +55,7 @@
             gemm_part2<DT, HT, NP, 1, 0, SE, kPreB>(accA, ph, pm, pipe, pa, NNR_FINISH(accB, NP, mwB, inv, pl, HR / 4, false), pre);
         }
         store_gates(mwB, li - 1, 1);
-        flush_max<TRAIN>(st, li - 1, lane, mx, mxa);
+        flush_max<TRAIN, NNR_STASH_ACT>(st, li - 1, lane, mx, mxa);
         init_acc(accB, bias, L::bias_off(li) + L::Dh, half);
         clear_mask(mwA);
         {   // pass B: half A of the new layer replaces pairs [0, NP) in place, one row behind the reads
@@ -77,7 +77,7 @@
         gemm_part2<DT, HT, NP, 1, 0, SE, kPreB>(accA, ph, pm, pipe, p0(F_L5HA), NNR_FINISH(accB, NP, mwB, inv, pl, HR / 4, false));
     }
     store_gates(mwB, 3, 1);
-    flush_max<TRAIN>(st, 3, lane, mx, mxa);
+    flush_max<TRAIN, NNR_STASH_ACT>(st, 3, lane, mx, mxa);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const u32x4 vh = __builtin_bit_cast(u32x4, park[q * 64]), vm = __builtin_bit_cast(u32x4, park[(4 + q) * 64]);

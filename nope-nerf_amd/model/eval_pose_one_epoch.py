@@ -1,10 +1,16 @@
 """Trainer_pose -- test-time pose optimisation step: network frozen in eval mode, no jitter, MSE on rgb, only the pose
 optimiser steps (reference model/eval_pose_one_epoch.py:10-98).  Needs d loss / d rays through the fused kernel with the
-weights held fixed."""
+weights held fixed.
+eval_pose.frozen_field (absent = true; a key the reference does not have): the model call runs under nnr.frozen_field() -- the render
+operator's frozen-field mode: no activation stash, no weight gradient.  Loss and pose gradients are unchanged bit for
+bit; the field's parameters get no .grad from a step (nothing reads it).  false: the full training path of the operator, as before.  On CPU
+tensors (the oracle backend) the key changes nothing."""
+import contextlib
 import logging
 
 import torch
 
+import nnr
 from model import imaging
 from model.common import arange_pixels
 from model.losses import Loss_Eval
@@ -26,6 +32,8 @@ class Trainer_pose(object):
         self.rendering_technique, self.n_points = cfg['type'], cfg['n_points']
         self.model, self.device = model, device
         self.pose_param_net, self.optimizer_pose, self.focal_net = pose_param_net, optimizer_pose, focal_net
+        frozen = cfg.get('frozen_field', True) if hasattr(cfg, 'get') else True
+        self.frozen_field = True if frozen is None else bool(frozen)
 
     def train_step(self, data, it=100000):
         """One Adam step on the pose table only; the radiance field (and a learned focal) stay frozen in eval mode."""
@@ -52,6 +60,7 @@ class Trainer_pose(object):
             camera_mat = imaging.camera_from_focal(self.focal_net(0), self.device)
         world_mat = imaging.inverse_pose(self.pose_param_net(img_idx))
         ray_idx, rgb_gt, p = _pixel_batch(img, self.n_points)
-        out = self.model(p, ray_idx, camera_mat, world_mat, scale_mat, self.rendering_technique, it=it, eval_mode=True,
-                         depth_img=depth_img, add_noise=False, img_size=tuple(img.shape[-2:]))
+        with (nnr.frozen_field() if self.frozen_field else contextlib.nullcontext()):
+            out = self.model(p, ray_idx, camera_mat, world_mat, scale_mat, self.rendering_technique, it=it, eval_mode=True,
+                             depth_img=depth_img, add_noise=False, img_size=tuple(img.shape[-2:]))
         return self.loss(out['rgb'], rgb_gt)

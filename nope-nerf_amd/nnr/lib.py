@@ -77,6 +77,8 @@ FUSION_EXPORTS = ("nnr_render_depth", "nnr_tsdf_integrate")
 SPARSE_EXPORTS = ("nnr_render_sparse",)
 #: include/nnr_regularise.h: the ray-distortion regulariser on the compositing weights, also under ABI 8
 REGULARISE_EXPORTS = ("nnr_ray_distortion_fwd", "nnr_ray_distortion_bwd")
+#: include/nnr_frozen.h: the frozen-field render (ray gradients only, no stash, no weight gradient), also under ABI 8
+FROZEN_EXPORTS = ("nnr_frozen_workspace_floats", "nnr_frozen_ws_plane", "nnr_frozen_fwd", "nnr_frozen_bwd")
 
 
 class Cfg(C.Structure):
@@ -195,9 +197,15 @@ def load():
     lib.nnr_render_sparse.argtypes = [cfgp] + [vp] * 6 + [C.POINTER(f32), C.POINTER(f32), C.POINTER(i32)] + [vp] * 7
     lib.nnr_ray_distortion_fwd.argtypes = [cfgp, vp, i32, vp, f32, f32, vp, vp]
     lib.nnr_ray_distortion_bwd.argtypes = [cfgp, vp, i32, vp, f32, f32, vp, vp, i32, i32, vp]
+    lib.nnr_frozen_workspace_floats.restype = C.c_size_t
+    lib.nnr_frozen_workspace_floats.argtypes = [cfgp]
+    lib.nnr_frozen_ws_plane.restype = i64
+    lib.nnr_frozen_ws_plane.argtypes = [cfgp, C.c_int, C.POINTER(C.c_int32)]
+    lib.nnr_frozen_fwd.argtypes = [cfgp] + [vp] * 13
+    lib.nnr_frozen_bwd.argtypes = [cfgp] + [vp] * 8
     lib.nnr_prof_begin.argtypes = [i32]
     lib.nnr_prof_end.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-    for n in EXPORTS + GEOMETRY_EXPORTS + FUSION_EXPORTS + SPARSE_EXPORTS + REGULARISE_EXPORTS:
+    for n in EXPORTS + GEOMETRY_EXPORTS + FUSION_EXPORTS + SPARSE_EXPORTS + REGULARISE_EXPORTS + FROZEN_EXPORTS:
         if not hasattr(lib, n):
             raise RuntimeError(f"libnnr.so does not export {n}")
     if lib.nnr_abi_version() != ABI_VERSION:

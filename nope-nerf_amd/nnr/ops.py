@@ -7,7 +7,10 @@ PyTorch is used for device memory, the current stream and the autograd graph edg
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import logging
+import threading
 import weakref
 from typing import List, Optional, Sequence
 
@@ -103,19 +106,20 @@ def _cfg_key(cfg: L.Cfg, device):
     return (str(device), cfg.n_rays, cfg.n_samples, cfg.hidden, cfg.flags)
 
 
-def _take_workspace(cfg: L.Cfg, device) -> torch.Tensor:
-    key = _cfg_key(cfg, device)
+def _take_workspace(cfg: L.Cfg, device, frozen: bool = False) -> torch.Tensor:
+    """frozen: the frozen-field workspace of include/nnr_frozen.h (its own pool entries: the same cfg, a far smaller buffer)."""
+    key = _cfg_key(cfg, device) + (("frozen",) if frozen else ())
     pool = _ws_pool.setdefault(key, [])
     if pool:
         return pool.pop()
-    n = L.load().nnr_workspace_floats(C.byref(cfg))
+    n = (L.load().nnr_frozen_workspace_floats if frozen else L.load().nnr_workspace_floats)(C.byref(cfg))
     if n == 0:
         raise RuntimeError("nnr: unsupported configuration (hidden_dim must be 128 or 256; num_points <= 1024 for training)")
     return torch.empty(n, dtype=torch.float32, device=device)
 
 
-def _give_workspace(cfg: L.Cfg, device, ws: torch.Tensor):
-    pool = _ws_pool.setdefault(_cfg_key(cfg, device), [])
+def _give_workspace(cfg: L.Cfg, device, ws: torch.Tensor, frozen: bool = False):
+    pool = _ws_pool.setdefault(_cfg_key(cfg, device) + (("frozen",) if frozen else ()), [])
     if len(pool) < 2:
         pool.append(ws)
 
@@ -333,10 +337,88 @@ def flat_grads_of(storage_ptr: int):
     return hit[0](), hit[1]
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# the frozen-field operator (include/nnr_frozen.h): the rays are differentiated, the field is a constant
+# ----------------------------------------------------------------------------------------------------------------------
+class _RenderRaysFrozen(torch.autograd.Function):
+    """render_rays(frozen=True) where the frozen kernels apply: nnr_frozen_fwd / nnr_frozen_bwd on the frozen workspace.  The parameters are
+    not inputs of the node (they reach it through opts, for the pack cache): autograd has no edge to them, their .grad stay None."""
+
+    @staticmethod
+    def forward(ctx, pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts):
+        _require_gpu(pts_o)
+        dev = pts_o.device
+        R, N = pts_o.shape[0], z_lo.shape[0]
+        cfg = L.make_cfg(R, N, opts["hidden"], dist_alpha=opts["dist_alpha"], white_bg=opts["white_bg"], relu_sigma=opts["relu_sigma"], train=True)
+        lib = L.load()
+        f32 = dict(dtype=torch.float32, device=dev)
+        pts_o, pts_d, view_d = (t.detach().contiguous().float() for t in (pts_o, pts_d, view_d))
+        z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
+        jit = jitter.detach().contiguous().float().view(R, N) if jitter is not None else None
+        packed = _packed_for(cfg, *opts["params"])
+        ws = _take_workspace(cfg, dev, frozen=True)
+        rgb, dist = torch.empty(R, 3, **f32), torch.empty(R, **f32)
+        alpha, zv = torch.empty(R, N, **f32), torch.empty(R, N, **f32)
+        L.check(lib.nnr_frozen_fwd(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(view_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), L.ptr(packed),
+                                   L.ptr(rgb), L.ptr(dist), L.ptr(alpha), L.ptr(zv), L.ptr(ws), L.stream()), "nnr_frozen_fwd")
+        ctx.cfg, ctx.ws, ctx.packed, ctx.dev = cfg, ws, packed, dev
+        ctx.mark_non_differentiable(alpha, zv)
+        ctx.set_materialize_grads(False)
+        return rgb, dist, alpha, zv
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_dist, _da, _dz):
+        cfg, ws, dev = ctx.cfg, ctx.ws, ctx.dev
+        if ws is None:
+            raise RuntimeError("nnr: backward called twice on the same render (workspace already released)")
+        R = cfg.n_rays
+        f32 = dict(dtype=torch.float32, device=dev)
+        d_rgb = (d_rgb if d_rgb is not None else torch.zeros(R, 3, **f32)).contiguous().float()
+        d_dist = (d_dist if d_dist is not None else torch.zeros(R, **f32)).contiguous().float()
+        d_o, d_d, d_v = (torch.empty(R, 3, **f32) for _ in range(3))
+        L.check(L.load().nnr_frozen_bwd(C.byref(cfg), L.ptr(ctx.packed), L.ptr(d_rgb), L.ptr(d_dist), L.ptr(d_o), L.ptr(d_d), L.ptr(d_v),
+                                        L.ptr(ws), L.stream()), "nnr_frozen_bwd")
+        ctx.ws = None
+        _give_workspace(cfg, dev, ws, frozen=True)
+        need = ctx.needs_input_grad
+        return (d_o if need[0] else None, d_d if need[1] else None, d_v if need[2] else None, None, None, None, None)
+
+
+_frozen_state = threading.local()      # .on: inside nnr.frozen_field() on this thread
+_frozen_said = set()                   # the reasons already logged: one line each per process
+_log = logging.getLogger("nnr")
+
+
+@contextlib.contextmanager
+def frozen_field():
+    """Inside the block, on this thread, every render_rays call with frozen=None behaves as frozen=True: the field's weights and biases are
+    constants, the rays are differentiated (test-time pose refinement: model.Trainer_pose).  Nests; restores the previous state on exit."""
+    prev = getattr(_frozen_state, "on", False)
+    _frozen_state.on = True
+    try:
+        yield
+    finally:
+        _frozen_state.on = prev
+
+
+def _frozen_fallback_reason(pts_o, pts_d, view_d, bf16):
+    """Why the frozen kernels do not apply to this call (None: they do).  They exist for the two-term fp16 products alone, and only a call
+    that differentiates a ray input has a use for them."""
+    if bf16:
+        return "bf16=True has no frozen kernels"
+    if L.fp32_products() != "split2":
+        return "NNR_FP32_PRODUCTS=%s has no frozen kernels (only split2 has)" % L.fp32_products()
+    if not torch.is_grad_enabled():
+        return "gradients are disabled"
+    if not any(t.requires_grad for t in (pts_o, pts_d, view_d)):
+        return "no ray input requires a gradient"
+    return None
+
+
 def render_rays(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor,
                 jitter: Optional[torch.Tensor], weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], *,
                 hidden: int, dist_alpha: bool, white_bg: bool, relu_sigma: bool, bf16: bool = False, samples: bool = True,
-                ray_distortion=None):
+                ray_distortion=None, frozen: Optional[bool] = None):
     """(R,3) sampling origin / direction / view direction, (N) z interval tables, optional (R,N) jitter, the 12
     nn.Linear weights and biases in state_dict order  ->  rgb (R,3), dist (R), alpha (R,N), z (R,N).
     Differentiable w.r.t. pts_o, pts_d, view_d, weights, biases.  bf16: bf16-MFMA products (fp32 accumulation) in the MLP
@@ -344,11 +426,29 @@ def render_rays(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor, 
     alpha and z come back as None and the renderer composites inside the MLP kernel (16 bytes written per ray).
     ray_distortion=(s_near, s_inv) (default None: nothing changes): where gradients are needed, a fifth, differentiable output dloss (R,), the
     ray distortion of every ray's compositing weights at the normalised depths (z - s_near) * s_inv (include/nnr_regularise.h); its gradient
-    reaches everything the other outputs' do.  Without gradients (torch.no_grad, or no input that requires one) the fifth output is None."""
+    reaches everything the other outputs' do.  Without gradients (torch.no_grad, or no input that requires one) the fifth output is None.
+    frozen=True (default None: False, or True inside nnr.frozen_field()): the field is FROZEN -- weights and biases are constants, their
+    gradients are None; outputs and the gradients of pts_o, pts_d, view_d are unchanged bit for bit.  The operator then runs the frozen
+    kernels on the frozen workspace (include/nnr_frozen.h: no activation stash, no weight gradient, a workspace some 24 times smaller at
+    hidden 256).  Where those do not apply (bf16=True, NNR_FP32_PRODUCTS other than split2, gradients disabled, no ray input that requires a
+    gradient) today's kernels run with the weights detached, and one logged line (logger "nnr") says why.  Never inferred from requires_grad.
+    frozen=True with ray_distortion raises ValueError: the regulariser is a training term."""
+    if frozen is None:
+        frozen = getattr(_frozen_state, "on", False)
+    if frozen and ray_distortion is not None:
+        raise ValueError("nnr: render_rays(frozen=True) takes no ray_distortion: the regulariser is a term of the field's training")
     opts = dict(hidden=hidden, dist_alpha=dist_alpha, white_bg=white_bg, relu_sigma=relu_sigma, bf16=bool(bf16), samples=bool(samples),
                 params=(list(weights), list(biases)))    # the caller's own tensor objects: identity keys the pack cache
     if ray_distortion is not None:
         opts["ray_distortion"] = _ray_distortion_range(ray_distortion)
+    if frozen:
+        why = _frozen_fallback_reason(pts_o, pts_d, view_d, bool(bf16))
+        if why is None:
+            return _RenderRaysFrozen.apply(pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts)
+        if why not in _frozen_said:
+            _frozen_said.add(why)
+            _log.info("nnr: render_rays(frozen=True) runs the training kernels with detached weights: %s", why)
+        weights, biases = [w.detach() for w in weights], [b.detach() for b in biases]      # (opts["params"] keeps the caller's objects: the pack cache's key)
     if not torch.is_grad_enabled():
         # forward-only (eval / visualisation inside torch.no_grad): no stash, small workspace
         return _RenderRays.apply(pts_o.detach(), pts_d.detach(), view_d.detach(), z_lo, z_hi, jitter, opts,

@@ -108,11 +108,12 @@ def pose_errors(pose_net, gt_poses, n_views):
     return {"ate": float(compute_ATE(gt, aligned)), "rpe_trans_x100": float(rpe_t * 100), "rpe_rot_deg": float(np.degrees(rpe_r))}
 
 
-def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_points=1024):
+def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_points=1024, frozen_field=True):
     """What reference evaluation/eval.py:54-186 does for the held-out views: initialise their poses from the learned training
     trajectory (init_method 'pre': the training pose just before each held-out frame), optimise them against the frozen field
     (Trainer_pose, Adam 1e-3 halved five times), then render every held-out frame in full and score it.  LPIPS needs a VGG
-    checkpoint and is reported as 0."""
+    checkpoint and is reported as 0.  frozen_field (eval_pose.frozen_field; --no-frozen-eval: False): the refinement steps run the render
+    operator's frozen-field mode -- same losses and poses, no weight gradient; the path taken is printed."""
     import dataloading as dl
     import model as mdl
     from model.eval_images import Eval_Images
@@ -127,7 +128,10 @@ def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_poi
     eval_pose = mdl.LearnPose(f.N_imgs, True, True, cfg, init_c2w=init).to(device)
     opt = torch.optim.Adam(eval_pose.parameters(), lr=1e-3)
     sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=list(range(0, epochs, max(1, epochs // 5))), gamma=0.5)
-    tp = mdl.Trainer_pose(nope, {"n_points": n_points, "type": "nope_nerf"}, device=device, optimizer_pose=opt, pose_param_net=eval_pose)
+    tp = mdl.Trainer_pose(nope, {"n_points": n_points, "type": "nope_nerf", "frozen_field": bool(frozen_field)}, device=device,
+                          optimizer_pose=opt, pose_param_net=eval_pose)
+    print(json.dumps({"eval_pose_path": "frozen field (nnr.frozen_field: no activation stash, no weight gradient)" if tp.frozen_field
+                      else "full training path (eval_pose.frozen_field: false)"}), flush=True)
     first = last = None
     for e in range(epochs):
         l2 = torch.stack([tp.train_step(batch)["loss"].detach() for batch in loader]).mean()
@@ -217,7 +221,7 @@ def occupancy_compare(cfg, nope, pose, loader, field, device, resolution, alpha_
 
 
 def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=None, eval_epochs=0, eval_dir=None, checkpoint_dir=None,
-        occupancy=None, **cfg_kw):
+        occupancy=None, frozen_eval=True, **cfg_kw):
     """-> dict with the per-epoch PSNR / pose-error curve and the loop throughput (+ novel-view scores with eval_epochs > 0)."""
     import dataloading as dl
     from model.common import mse2psnr
@@ -267,7 +271,8 @@ def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=No
     if eval_epochs > 0:
         import tempfile
         with tempfile.TemporaryDirectory() as tmp:
-            novel = novel_view_eval(cfg, trainer.model, pose, field, device, eval_epochs, eval_dir or tmp, n_points=min(1024, n_rays))
+            novel = novel_view_eval(cfg, trainer.model, pose, field, device, eval_epochs, eval_dir or tmp, n_points=min(1024, n_rays),
+                                    frozen_field=frozen_eval)
     occ_rows = None
     if occupancy is not None:      # (resolution, [alpha_min, ...]): dense against sparse evaluation frames
         if num_fine_of(cfg):
@@ -306,6 +311,8 @@ def main():
                     help="training.ray_distortion_weight: the weight of the ray distortion of the compositing weights (0 = off; e.g. 0.01)")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--eval-epochs", type=int, default=0, help="test-time pose optimisation epochs before scoring the held-out views")
+    ap.add_argument("--no-frozen-eval", action="store_true",
+                    help="eval_pose.frozen_field: false -- refine the held-out views' poses on the operator's full training path instead of its frozen-field mode")
     ap.add_argument("--eval-dir", default=None, help="where the rendered held-out frames go (default: a temporary directory)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--checkpoint-dir", default=None, help="write model.pt, model_pose.pt and config.yaml here after the last epoch (tools/extract_mesh.py takes DIR/config.yaml)")
@@ -316,7 +323,7 @@ def main():
     res = run(a.path, a.scene, style=a.style, epochs=a.epochs, log_every=a.log_every, eval_epochs=a.eval_epochs, eval_dir=a.eval_dir, checkpoint_dir=a.checkpoint_dir, n_rays=a.rays, n_samples=a.samples,
               hidden=a.hidden, resident=not a.host_loader, aux=not a.no_aux, resize_factor=a.factor, workers=a.workers,
               mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine, proposal=a.proposal, occupancy=occupancy,
-              ray_distortion=a.ray_distortion)
+              ray_distortion=a.ray_distortion, frozen_eval=not a.no_frozen_eval)
     print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
