@@ -20,6 +20,9 @@ SOURCES = [("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MOD
            # the frozen-field variants (include/nnr_frozen.h): the training forward and the input gradient without their stashes, one unit per D
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=2")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_STASH=0")),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=2")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=128", "NNR_DGRAD_STASH=0")),
+           # the list-driven frozen variants (include/nnr_frozen_sparse.h): the same two kernels walking a device-built list of live samples
+           ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=3")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_STASH=0", "NNR_DGRAD_LIST=1")),
+           ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=3")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=128", "NNR_DGRAD_STASH=0", "NNR_DGRAD_LIST=1")),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=128",)),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_sparse_f16.hip", ()), ("nnr_march_f16.hip", ()), ("nnr_propose_f16.hip", ()), ("nnr_grid_f16.hip", ()), ("nnr_bricks_f16.hip", ()),
            ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_MODE=2")),
@@ -50,6 +53,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-prag
 # prologue values in scratch, reloaded at pass start (where the pass waits for its inputs anyway), nothing inside a pass; the inference forward (no stores in flight) may spill its composite carry.
 # (three-term kernels: only the D = 256 training forward keeps a few pass-start values in scratch, 32 bytes)
 SCRATCH_LIMIT = {"18mlp_fwd_f16_kernelI": 0, "18mlp_fwd_f16_kernelILi256ELb0E": 48, "18mlp_fwd_f16_kernelILi128ELb0E": 48,      # (inference: prologue values and the composite carry, outside the MFMA streams)
+                 "30mlp_fwd_frozen_list_f16_kernelI": 0, "25mlp_dgrad_list_f16_kernelI": 0,      # (the list-driven frozen pair: include/nnr_frozen_sparse.h)
                  "25mlp_fwd_frozen_f16_kernelI": 0,      # (the frozen-field forward; its input gradient is mlp_dgrad_f16_kernel<D, false>: the next key)
                  "20mlp_dgrad_f16_kernelI": 0, "14mlp_fwd_kernelI": 0, "14mlp_fwd_kernelILi256ELb1ELi2E": 48, "16mlp_dgrad_kernelI": 0, "12wgrad_kernelI": 0, "14wgrad_b_kernelE": 0,
                  "19mlp_fwd_bf16_kernelI": 48, "19mlp_fwd_bf16_kernelILi256ELb1E": 16, "19mlp_fwd_bf16_kernelILi128ELb1E": 16,

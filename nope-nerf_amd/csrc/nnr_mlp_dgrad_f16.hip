@@ -18,8 +18,23 @@
 // for a weight gradient -- no store to P_DH1..8 / P_DG, no zeroing of the padded rows of P_DOUT4, no plane maxima.  The per-sample scale and
 // recentre() live in registers and are what they are in the stashing build, so the two builds' outputs are equal bit for bit.  ws_dh, ws_dg and
 // plane_max are null in its argument block (nnr_frozen_api.cpp): every store through them is compiled out, none is guarded at run time.
+// LIST (csrc/build.py: NNR_DGRAD_LIST=1 beside NNR_DGRAD_STASH=0) is the LIST-DRIVEN frozen build mlp_dgrad_list_f16_kernel of the sparse
+// frozen-field render (include/nnr_frozen_sparse.h): flat mode only, slot s of the COMPACTED order takes the sample
+// live[min(s, n_live - 1)].  P_XE, P_XF and P_MASK are read by the compact chunk, as its forward wrote them; P_DOUT4 is read and P_DPTS /
+// P_DVIEW are written at the sample's dense index.  A slot past n_live takes zero gradients and stores nothing; a workgroup whose first
+// slot is past n_live returns before the weight stream starts.
+#if defined(NNR_DGRAD_LIST) && NNR_DGRAD_LIST == 1
+#define NNR_DGRAD_KERNEL mlp_dgrad_list_f16_kernel
+#define NNR_DGRAD_ARGS MlpDgradListArgs
+#define NNR_DGRAD_IS_LIST true
+#else
+#define NNR_DGRAD_KERNEL mlp_dgrad_f16_kernel
+#define NNR_DGRAD_ARGS MlpDgradArgs
+#define NNR_DGRAD_IS_LIST false
+#endif
 #include "nnr_device.h"
 #include "nnr_frozen_kernels.h"
+#include "nnr_frozen_sparse_kernels.h"
 #include "nnr_kernels.h"
 #include "nnr_split2.h"
 
@@ -78,7 +93,9 @@ __device__ __forceinline__ f32x4 enc_backward(const G& g, const float (&pv)[NR],
 }  // namespace f16dg
 
 template <int D, bool STASH>
-__global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
+__global__ __launch_bounds__(256, 1) void NNR_DGRAD_KERNEL(NNR_DGRAD_ARGS a) {
+    constexpr bool LIST = NNR_DGRAD_IS_LIST;      // the samples come from a live list (the sparse frozen-field render)
+    static_assert(!(LIST && STASH), "the list-driven build is a frozen build");
     using L = Layout<D, 3>;
     using Pipe = Split2PipeT<false>;
     constexpr int kRingF4 = kNBuf * Pipe::F4;
@@ -103,9 +120,14 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
     __shared__ uint32_t wg_max[9];      // the workgroup's largest |gradient| per plane P_DH1..8 ([0..8)) and P_DG ([8]), as integers
     if (STASH && threadIdx.x < 9) wg_max[threadIdx.x] = 0;
     __syncthreads();   // before any DMA is in flight: the only full barrier in front of the passes
+    int n_live = 0;
+    if constexpr (LIST) {
+        n_live = __builtin_amdgcn_readfirstlane(*list_n_live(a));
+        if ((int)blockIdx.x * kBlockSamples >= n_live) return;      // workgroup-uniform, and no DMA is in flight yet
+    }
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     Pipe pipe{reinterpret_cast<const f32x4*>(a.packed + L::bwd_base) + wave_u * (Pipe::PW * 64), smem, wave_u, lane0, L::bwd_panels};
-    const int n_pass = a.chunks_per_ray > 0 ? a.chunks_per_ray : 1;
+    const int n_pass = LIST ? 1 : a.chunks_per_ray > 0 ? a.chunks_per_ray : 1;
     pipe.more = n_pass > 1;
     pipe.start();
     auto p0 = [&](int part) { return L::bwd_panel0(part); };
@@ -125,11 +147,13 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
     const int64_t chunk = a.chunks_per_ray > 0 ? ((int64_t)blockIdx.x * kWavesPerBlock + wave_u) * n_pass + pass
                                                 : (int64_t)blockIdx.x * kWavesPerBlock + wave_u;
     const int64_t s = chunk * kChunk + col;
-    const bool live = s < a.S;  // padded samples carry zero gradients so they add nothing to the weight gradients
+    const bool live = LIST ? (int)s < n_live : s < a.S;  // padded samples carry zero gradients so they add nothing to the weight gradients
+    int64_t sd = s;             // where the sample's rows of P_DOUT4, P_DPTS and P_DVIEW are (LIST: its dense index; s stays the compact slot)
+    if constexpr (LIST) sd = list_live(a)[live ? (int)s : n_live - 1];
     const uint32_t* mask_base = a.ws_mask + ((chunk * L::n_mask_layers) * 64 + lane) * L::mask_words;
 
     f32x4 dout = {0.f, 0.f, 0.f, 0.f};
-    if (live) dout = *reinterpret_cast<const f32x4*>(a.ws_dout4 + 4 * s);
+    if (live) dout = *reinterpret_cast<const f32x4*>(a.ws_dout4 + 4 * sd);
     else if constexpr (STASH) {
         if (half == 0) *reinterpret_cast<f32x4*>(a.ws_dout4 + 4 * s) = dout;   // padded rows feed the weight-gradient kernel: zero them
     }
@@ -264,7 +288,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
         gemm_part2<HT, 1>(accd, gh, gm, pipe, p0(B_RGBH_D));
         const float c = inv_scale(8) * sInv;
         const f32x4 gv = f16dg::enc_backward<16>([&](int r) { return accd[0][r] * c; }, pvd, half);
-        if (half == 0 && live) *reinterpret_cast<f32x4*>(a.ws_dview + 4 * s) = gv;
+        if (half == 0 && live) *reinterpret_cast<f32x4*>(a.ws_dview + 4 * sd) = gv;
     }
 
     // ---- trunk ----
@@ -346,7 +370,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
             for (int i = 0; i < 4; ++i) de[4 * q + i] = acc2[q >> 2][4 * (q & 3) + i] * c1 + v[i] * c4;
         }
         const f32x4 gp = f16dg::enc_backward<32>([&](int r) { return de[r]; }, pve, half);
-        if (half == 0 && live) *reinterpret_cast<f32x4*>(a.ws_dpts + 4 * s) = gp;
+        if (half == 0 && live) *reinterpret_cast<f32x4*>(a.ws_dpts + 4 * sd) = gp;
     }
 #undef NNR_SELECT
     pipe.next_pass(pass + 2 < n_pass);
@@ -358,7 +382,14 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_f16_kernel(MlpDgradArgs a) {
 }
 
 // one (D, STASH) per translation unit (csrc/build.py: -DNNR_DGRAD_D=.. [-DNNR_DGRAD_STASH=0]), as for nnr_mlp_dgrad.hip
-#if defined(NNR_DGRAD_D) && defined(NNR_DGRAD_STASH) && NNR_DGRAD_STASH == 0
+#if defined(NNR_DGRAD_D) && NNR_DGRAD_IS_LIST
+template <>
+hipError_t launch_mlp_dgrad_frozen_list_variant<NNR_DGRAD_D>(const MlpDgradListArgs& a, hipStream_t st) {
+    dim3 grid((unsigned)(a.S_pad / kBlockSamples)), block(256);      // the dense grid: the host does not know n_live
+    hipLaunchKernelGGL((mlp_dgrad_list_f16_kernel<NNR_DGRAD_D, false>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+#elif defined(NNR_DGRAD_D) && defined(NNR_DGRAD_STASH) && NNR_DGRAD_STASH == 0
 template <>
 hipError_t launch_mlp_dgrad_frozen_variant<NNR_DGRAD_D>(const MlpDgradArgs& a, hipStream_t st) {
     dim3 grid((unsigned)(a.chunks_per_ray > 0 ? a.S_pad / kBlockSamples / a.chunks_per_ray : a.S_pad / kBlockSamples)), block(256);

@@ -11,22 +11,39 @@
 // encoding planes, z and the outputs -- keeps the range guard, and neither stores the hidden and colour-hidden activations nor keeps the
 // plane maxima: both exist for the weight gradient alone.  Its argument block carries null pointers for those planes (nnr_frozen_api.cpp);
 // every store through them is compiled out (NNR_STASH_ACT, nnr_trunk_f16.h), none is guarded at run time.
-#if defined(NNR_FWD_TRAIN) && NNR_FWD_TRAIN == 2
+// A fourth build (NNR_FWD_TRAIN=3), the LIST-DRIVEN frozen forward mlp_fwd_frozen_list_f16_kernel of the sparse frozen-field render
+// (include/nnr_frozen_sparse.h): flat mode only, slot s of the COMPACTED order takes the sample live[min(s, n_live - 1)]
+// of a device-built list.  P_XE, P_XF and P_MASK stay indexed by the compact chunk (private to this kernel and its input gradient); P_OUT4 is
+// written at the sample's dense index; z is the compaction kernel's.  A slot past n_live stores nothing to P_OUT4; a workgroup whose first
+// slot is past n_live returns before the weight stream starts.  A sample whose point is not finite comes out NaN (the other builds leave it
+// to ReLU, which makes it finite): its ray is NaN, as in the sparse inference render.
+#if defined(NNR_FWD_TRAIN) && NNR_FWD_TRAIN == 3
+#define NNR_STASH_ACT false
+#define NNR_FWD_KERNEL mlp_fwd_frozen_list_f16_kernel
+#define NNR_FWD_ARGS MlpFwdListArgs
+#define NNR_FWD_LIST 1
+#elif defined(NNR_FWD_TRAIN) && NNR_FWD_TRAIN == 2
 #define NNR_STASH_ACT false
 #define NNR_FWD_KERNEL mlp_fwd_frozen_f16_kernel
+#define NNR_FWD_ARGS MlpFwdArgs
+#define NNR_FWD_LIST 0
 #else
 #define NNR_FWD_KERNEL mlp_fwd_f16_kernel
+#define NNR_FWD_ARGS MlpFwdArgs
+#define NNR_FWD_LIST 0
 #endif
 #include "nnr_trunk_f16.h"
 #include "nnr_frozen_kernels.h"
+#include "nnr_frozen_sparse_kernels.h"
 
 namespace nnr {
 
 static_assert(kTileActPlanes, "the activation planes of a three-term / two-term training workspace are tile-major");
 
 template <int D, bool TRAIN>
-__global__ __launch_bounds__(256, 1) void NNR_FWD_KERNEL(MlpFwdArgs a) {
+__global__ __launch_bounds__(256, 1) void NNR_FWD_KERNEL(NNR_FWD_ARGS a) {
     constexpr bool STASH = NNR_STASH_ACT;      // the kernel stores the activation planes and keeps their maxima
+    constexpr bool LIST = NNR_FWD_LIST;       // the samples come from a live list (the sparse frozen-field render)
     using L = Layout<D, 3>;
     using Pipe = Split2PipeT<false>;
     constexpr int kRingF4 = kNBuf * Pipe::F4;
@@ -41,9 +58,14 @@ __global__ __launch_bounds__(256, 1) void NNR_FWD_KERNEL(MlpFwdArgs a) {
     __shared__ uint32_t wg_max[9];      // training: the workgroup's largest stashed value per activation plane P_XH1..8 (as integers: the values are >= 0); [8]: the position encoding's
     if (STASH && threadIdx.x < 9) wg_max[threadIdx.x] = 0;
     __syncthreads();   // before any DMA is in flight: the only full barrier in front of the passes
+    int n_live = 0;
+    if constexpr (LIST) {
+        n_live = __builtin_amdgcn_readfirstlane(*list_n_live(a));
+        if ((int)blockIdx.x * kBlockSamples >= n_live) return;      // workgroup-uniform, and no DMA is in flight yet
+    }
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     Pipe pipe{reinterpret_cast<const f32x4*>(a.packed) + wave_u * (Pipe::PW * 64), smem, wave_u, lane0, L::fwd_panels};
-    const int n_pass = a.chunks_per_ray > 0 ? a.chunks_per_ray : 1;
+    const int n_pass = LIST ? 1 : a.chunks_per_ray > 0 ? a.chunks_per_ray : 1;
     pipe.more = n_pass > 1;
     pipe.start();
     float cT = 1.f, cr = 0.f, cg = 0.f, cb = 0.f, cz = 0.f, cw = 0.f;      // fused compositing (inference, ray mode), carried across the chunks
@@ -58,10 +80,21 @@ __global__ __launch_bounds__(256, 1) void NNR_FWD_KERNEL(MlpFwdArgs a) {
     const int col = lane & 31;
     const int64_t chunk_id = a.chunks_per_ray > 0 ? ((int64_t)blockIdx.x * kWavesPerBlock + wave_u) * n_pass + pass
                                                    : (int64_t)blockIdx.x * kWavesPerBlock + wave_u;
+#if NNR_FWD_LIST      // (the preprocessor, not `if constexpr`: the other builds keep their text, and with it their listings, to the letter)
+    const int slot = (int)chunk_id * kChunk + col;                                 // this lane's slot of the compacted order
+    const bool in_list = slot < n_live;                                            // a slot past the list recomputes the list's last sample and stores nothing
+    const int64_t s = list_live(a)[in_list ? slot : n_live - 1];                   // this lane's sample: its dense index
+    const int64_t sc = s;
+    const int ray = (int)sc / a.N;
+    const int j = (int)sc - ray * a.N;
+#define NNR_FWD_STORES in_list
+#else
     const int64_t s = chunk_id * kChunk + col;                                     // this lane's sample
     const int64_t sc = s < a.S ? s : a.S - 1;                                      // clamp: padded samples recompute the last one
     const int ray = (int)(sc / a.N);
     const int j = (int)(sc - (int64_t)ray * a.N);
+#define NNR_FWD_STORES s < a.S
+#endif
     const int lane_off = 16 * lane;
 
     // ---- sampling (model/rendering.py:184-195).  Unfused mul/add to round exactly like the reference. ----
@@ -76,7 +109,14 @@ __global__ __launch_bounds__(256, 1) void NNR_FWD_KERNEL(MlpFwdArgs a) {
     const float pz = __fadd_rn(ro[2], __fmul_rn(rd[2], z));
     const float vx = rv[0], vy = rv[1], vz = rv[2];
     const bool fuse = !TRAIN && a.fuse_rgb != nullptr;
+#if NNR_FWD_LIST      // a sample whose point is not finite (outside every grid, hence live) is made NaN at the output, as in the sparse inference
+                      // render and the depth kernel: ReLU would turn its NaN activations into zeros and the sample out finite
+    const float kInfP = __uint_as_float(0x7f800000u);
+    const bool finite_p = fabsf(px) < kInfP && fabsf(py) < kInfP && fabsf(pz) < kInfP;
+#endif
+#if !NNR_FWD_LIST      // (LIST: the compaction kernel wrote z of every sample, by the same expressions)
     if (half == 0 && s < a.S && !fuse) a.ws_z[s] = z;
+#endif
     constexpr int HR = 16 * HT;              // registers of half a layer's outputs
     constexpr int NP = HR / 2;               // register pairs per half (the unit of hidden epilogue work)
     constexpr int HW = (HR + 31) / 32;       // mask words per half
@@ -150,13 +190,17 @@ __global__ __launch_bounds__(256, 1) void NNR_FWD_KERNEL(MlpFwdArgs a) {
         o[3] = sigma_raw;
         {   // a sample that saw an activation outside fp16's range (either of its two lanes) is made NaN here: the loss is NaN, the caller's
             // check fires (model/losses.py:204-205), an inference frame shows it
+#if NNR_FWD_LIST
+            const bool over = left_f16_range(TRAIN ? fmaxf(mxa, mx) : mx) || !finite_p;
+#else
             const bool over = left_f16_range(TRAIN ? fmaxf(mxa, mx) : mx);
+#endif
             const float qnan = __uint_as_float(0x7fc00000u);
 #pragma unroll
             for (int c = 0; c < 4; ++c) o[c] = over ? qnan : o[c];
         }
         if (!fuse) {
-            if (half == 0 && s < a.S) *reinterpret_cast<f32x4*>(a.ws_out4 + 4 * s) = o;
+            if (half == 0 && NNR_FWD_STORES) *reinterpret_cast<f32x4*>(a.ws_out4 + 4 * s) = o;
         } else if constexpr (!TRAIN) {
             // model/rendering.py:119-132,145-147 for the 32 samples of this chunk, as in nnr_mlp_fwd.hip (= composite_fwd_kernel 64 at a time)
             const int jn = j + 1;
@@ -185,6 +229,7 @@ __global__ __launch_bounds__(256, 1) void NNR_FWD_KERNEL(MlpFwdArgs a) {
         }
     }
 #undef NNR_FINISH
+#undef NNR_FWD_STORES
     pipe.next_pass(pass + 2 < n_pass);
     }   // pass
     if constexpr (STASH) {      // the workgroup's maxima to the launch's table (NNR_F_SPLIT2: the weight-gradient kernel's scales)
@@ -195,7 +240,14 @@ __global__ __launch_bounds__(256, 1) void NNR_FWD_KERNEL(MlpFwdArgs a) {
 }
 
 // One (D, TRAIN) instantiation per translation unit (csrc/build.py: -DNNR_FWD_D=.. -DNNR_FWD_TRAIN=..), as for nnr_mlp_fwd.hip
-#if defined(NNR_FWD_D) && NNR_FWD_TRAIN == 2
+#if defined(NNR_FWD_D) && NNR_FWD_TRAIN == 3
+template <>
+hipError_t launch_mlp_fwd_frozen_list_variant<NNR_FWD_D>(const MlpFwdListArgs& a, hipStream_t st) {
+    dim3 grid((unsigned)(a.S_pad / kBlockSamples)), block(256);      // the dense grid: the host does not know n_live
+    hipLaunchKernelGGL((mlp_fwd_frozen_list_f16_kernel<NNR_FWD_D, true>), grid, block, 0, st, a);
+    return hipGetLastError();
+}
+#elif defined(NNR_FWD_D) && NNR_FWD_TRAIN == 2
 template <>
 hipError_t launch_mlp_fwd_frozen_variant<NNR_FWD_D>(const MlpFwdArgs& a, hipStream_t st) {
     dim3 grid = mlp_fwd_grid(a), block(256);

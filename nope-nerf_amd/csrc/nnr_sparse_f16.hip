@@ -21,25 +21,10 @@
 // A wave past the last ray repeats the last ray and stores nothing.
 // LDS: the forward's (ring 3 panels, park 12 slots per lane, tables) + 4 x 256 bytes of lists + 4 counts.
 #include "nnr_trunk_f16.h"
+#include "nnr_sparse_cell.h"
 #include "nnr_sparse_kernels.h"
 
 namespace nnr {
-
-// the cell of a point: (i_z n_y + i_y) n_x + i_x, or -1 outside the grid; `word`, `bit`: its place in the bitfield
-__device__ __forceinline__ int sparse_cell(const SparseArgs& a, float px, float py, float pz, int& word, int& bit) {
-    const float fx = __fmul_rn(__fsub_rn(px, a.lo[0]), a.inv_step[0]);
-    const float fy = __fmul_rn(__fsub_rn(py, a.lo[1]), a.inv_step[1]);
-    const float fz = __fmul_rn(__fsub_rn(pz, a.lo[2]), a.inv_step[2]);
-    const bool inside = fx >= 0.f && fx < (float)a.n[0] && fy >= 0.f && fy < (float)a.n[1] && fz >= 0.f && fz < (float)a.n[2];
-    word = 0;
-    bit = 0;
-    if (!inside) return -1;
-    const int ix = (int)fx, iy = (int)fy, iz = (int)fz;
-    const int row = iz * a.n[1] + iy;
-    word = row * a.wx + (ix >> 5);
-    bit = ix & 31;
-    return row * a.n[0] + ix;
-}
 
 template <int D>
 __global__ __launch_bounds__(256, 1) void sparse_f16_kernel(SparseArgs a) {

@@ -4,7 +4,13 @@ weights held fixed.
 eval_pose.frozen_field (absent = true; a key the reference does not have): the model call runs under nnr.frozen_field() -- the render
 operator's frozen-field mode: no activation stash, no weight gradient.  Loss and pose gradients are unchanged bit for
 bit; the field's parameters get no .grad from a step (nothing reads it).  false: the full training path of the operator, as before.  On CPU
-tensors (the oracle backend) the key changes nothing."""
+tensors (the oracle backend) the key changes nothing.
+eval_pose.occupancy (absent = false: nothing changes; needs frozen_field): the FIRST step builds an occupancy grid of the field ONCE, from the
+rendering.occupancy settings (Renderer.frozen_occupancy_grid: geometry.occupancy_grid at level_for_alpha, the same bounds rules), keeps it
+for the trainer's lifetime and runs every step under nnr.frozen_field(occupancy=grid): the samples in cells the grid calls empty are skipped,
+forward and backward.  The grid is valid because the field is frozen by this trainer's own declaration; the pose
+optimiser's steps do not touch it.  Where the renderer refuses a grid (CPU tensors, bf16 products, too many samples) the dense frozen path
+runs."""
 import contextlib
 import logging
 
@@ -34,6 +40,11 @@ class Trainer_pose(object):
         self.pose_param_net, self.optimizer_pose, self.focal_net = pose_param_net, optimizer_pose, focal_net
         frozen = cfg.get('frozen_field', True) if hasattr(cfg, 'get') else True
         self.frozen_field = True if frozen is None else bool(frozen)
+        occupancy = cfg.get('occupancy', False) if hasattr(cfg, 'get') else False
+        self.occupancy = bool(occupancy) if occupancy is not None else False
+        if self.occupancy and not self.frozen_field:
+            raise ValueError("eval_pose.occupancy: true needs eval_pose.frozen_field (an occupancy grid is only valid for a frozen field)")
+        self.occupancy_grid, self.occupancy_builds = None, 0      # built by the first step, kept for the trainer's lifetime
 
     def train_step(self, data, it=100000):
         """One Adam step on the pose table only; the radiance field (and a learned focal) stay frozen in eval mode."""
@@ -60,7 +71,10 @@ class Trainer_pose(object):
             camera_mat = imaging.camera_from_focal(self.focal_net(0), self.device)
         world_mat = imaging.inverse_pose(self.pose_param_net(img_idx))
         ray_idx, rgb_gt, p = _pixel_batch(img, self.n_points)
-        with (nnr.frozen_field() if self.frozen_field else contextlib.nullcontext()):
+        if self.occupancy and self.occupancy_builds == 0:
+            self.occupancy_grid = self.model.renderer.frozen_occupancy_grid(img.device)
+            self.occupancy_builds = 1
+        with (nnr.frozen_field(occupancy=self.occupancy_grid) if self.frozen_field else contextlib.nullcontext()):
             out = self.model(p, ray_idx, camera_mat, world_mat, scale_mat, self.rendering_technique, it=it, eval_mode=True,
                              depth_img=depth_img, add_noise=False, img_size=tuple(img.shape[-2:]))
         return self.loss(out['rgb'], rgb_gt)

@@ -273,7 +273,22 @@ class Renderer(nn.Module):
         })
 
     # ------------------------------------------------------------------------------------------------ sparse inference render
-    def _occupancy_grid(self, pixels, z_lo, kw):
+    def frozen_occupancy_grid(self, device):
+        """eval_pose.occupancy (model.Trainer_pose): the occupancy grid of this renderer's field for nnr.frozen_field(occupancy=grid), from the
+        rendering.occupancy settings -- the same bounds rules, the same level (geometry.level_for_alpha), the same refusals other than
+        "gradients are enabled" (None where the dense path has to run; at most 1024 samples per ray here).  Built anew on every call and
+        not kept here: the caller owns it, and says the field is frozen."""
+        cfg = self.cfg
+        if cfg.get('occupancy', None) is None:
+            raise ValueError("eval_pose.occupancy: true needs the rendering.occupancy settings (resolution, alpha_min; DESIGN.md section 15)")
+        net = self.model
+        kw = dict(dist_alpha=bool(cfg['dist_alpha']), relu_sigma=(net.occ_activation != 'softplus'),
+                  bf16=(str(cfg.get('mfma_dtype', 'fp32')).lower() == 'bf16'))
+        n_render = int(cfg['num_points']) + int(cfg.get('num_fine', 0) or 0)
+        with torch.no_grad():
+            return self._occupancy_grid(torch.empty(0, device=device), torch.empty(n_render), kw, frozen=True)
+
+    def _occupancy_grid(self, pixels, z_lo, kw, frozen=False):
         """rendering.occupancy: {resolution: N, alpha_min: A, dilate: 1, bounds: [lo, hi]} -> the occupancy grid of the sparse inference render
         (model.geometry.occupancy_grid), or None where the dense path has to run (one logged line per reason).  N cells per axis over
         `bounds` (two scalars or two triples; default: the cube of rendering.radius under sample_option 'uniform'; required under 'ndc', where
@@ -286,13 +301,15 @@ class Renderer(nn.Module):
         occ = cfg['occupancy']
         n_render = int(z_lo.shape[0])
         why = None
-        if torch.is_grad_enabled():
+        if torch.is_grad_enabled() and not frozen:
             why = "gradients are enabled (the sparse render is forward-only)"
         elif not pixels.is_cuda:
             why = "the tensors are not on the GPU"
         elif kw['bf16']:
             why = "rendering.mfma_dtype is bf16 (the sparse kernel has two-term fp16 products only)"
-        elif n_render > 256:
+        elif frozen and n_render > 1024:
+            why = "%d samples per ray (the frozen kernels take at most 1024)" % n_render
+        elif not frozen and n_render > 256:
             why = "%d samples per ray (the sparse kernel takes at most 256)" % n_render
         if why is not None:
             seen = self.__dict__.setdefault('_occupancy_said', set())
@@ -313,7 +330,7 @@ class Renderer(nn.Module):
         w, b = net.weights(), net.biases()
         hit = self.__dict__.get('_occupancy_hit', None)
         key = (tuple(lo), tuple(hi), repr(occ.get('resolution')), float(occ['alpha_min']), int(occ.get('dilate', 1)), kw['dist_alpha'], kw['relu_sigma'])
-        if hit is not None and hit[0] == key and hit[1].matches(w, b):
+        if not frozen and hit is not None and hit[0] == key and hit[1].matches(w, b):
             return hit[2]
         n_coarse = cfg['num_points'] - cfg['outside_steps']
         near, far = (0., 1.) if cfg['sample_option'] == 'ndc' else (float(self.depth_range[0]), float(self.depth_range[1]))
@@ -321,6 +338,8 @@ class Renderer(nn.Module):
         level = geometry.level_for_alpha(occ['alpha_min'], delta, 'relu' if kw['relu_sigma'] else 'softplus')
         res = occ['resolution']
         grid = geometry.occupancy_grid(self, lo, hi, int(res) if not isinstance(res, (list, tuple)) else tuple(res), level, int(occ.get('dilate', 1)))
+        if frozen:      # (the caller's grid: no stamp -- the pose optimiser steps every iteration, and the field is frozen by declaration)
+            return grid
         stamp = _nnr_ops.ParamsStamp(w, b)      # (after the build: density_volume packs the weights if need be)
         self.__dict__['_occupancy_hit'] = (key, stamp, grid)
         self.occupancy_builds = getattr(self, 'occupancy_builds', 0) + 1

@@ -79,6 +79,10 @@ SPARSE_EXPORTS = ("nnr_render_sparse",)
 REGULARISE_EXPORTS = ("nnr_ray_distortion_fwd", "nnr_ray_distortion_bwd")
 #: include/nnr_frozen.h: the frozen-field render (ray gradients only, no stash, no weight gradient), also under ABI 8
 FROZEN_EXPORTS = ("nnr_frozen_workspace_floats", "nnr_frozen_ws_plane", "nnr_frozen_fwd", "nnr_frozen_bwd")
+#: include/nnr_frozen_sparse.h: the frozen-field render that skips the samples an occupancy grid calls empty, also under ABI 8
+FROZEN_SPARSE_EXPORTS = ("nnr_frozen_sparse_workspace_floats", "nnr_frozen_sparse_ws_plane", "nnr_frozen_sparse_fwd", "nnr_frozen_sparse_bwd")
+#: the int32 planes behind the frozen planes (nnr_frozen_sparse_ws_plane)
+FS_LIVE, FS_RAY_OFF, FS_N_LIVE, FS_RAY_COUNT, FS_RAY_MASK = 100, 101, 102, 103, 104
 
 
 class Cfg(C.Structure):
@@ -203,9 +207,15 @@ def load():
     lib.nnr_frozen_ws_plane.argtypes = [cfgp, C.c_int, C.POINTER(C.c_int32)]
     lib.nnr_frozen_fwd.argtypes = [cfgp] + [vp] * 13
     lib.nnr_frozen_bwd.argtypes = [cfgp] + [vp] * 8
+    lib.nnr_frozen_sparse_workspace_floats.restype = C.c_size_t
+    lib.nnr_frozen_sparse_workspace_floats.argtypes = [cfgp]
+    lib.nnr_frozen_sparse_ws_plane.restype = i64
+    lib.nnr_frozen_sparse_ws_plane.argtypes = [cfgp, C.c_int, C.POINTER(C.c_int32)]
+    lib.nnr_frozen_sparse_fwd.argtypes = [cfgp] + [vp] * 6 + [C.POINTER(f32), C.POINTER(f32), C.POINTER(i32)] + [vp] * 11
+    lib.nnr_frozen_sparse_bwd.argtypes = [cfgp] + [vp] * 8
     lib.nnr_prof_begin.argtypes = [i32]
     lib.nnr_prof_end.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-    for n in EXPORTS + GEOMETRY_EXPORTS + FUSION_EXPORTS + SPARSE_EXPORTS + REGULARISE_EXPORTS + FROZEN_EXPORTS:
+    for n in EXPORTS + GEOMETRY_EXPORTS + FUSION_EXPORTS + SPARSE_EXPORTS + REGULARISE_EXPORTS + FROZEN_EXPORTS + FROZEN_SPARSE_EXPORTS:
         if not hasattr(lib, n):
             raise RuntimeError(f"libnnr.so does not export {n}")
     if lib.nnr_abi_version() != ABI_VERSION:

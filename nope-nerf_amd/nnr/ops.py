@@ -106,20 +106,23 @@ def _cfg_key(cfg: L.Cfg, device):
     return (str(device), cfg.n_rays, cfg.n_samples, cfg.hidden, cfg.flags)
 
 
-def _take_workspace(cfg: L.Cfg, device, frozen: bool = False) -> torch.Tensor:
-    """frozen: the frozen-field workspace of include/nnr_frozen.h (its own pool entries: the same cfg, a far smaller buffer)."""
-    key = _cfg_key(cfg, device) + (("frozen",) if frozen else ())
+def _take_workspace(cfg: L.Cfg, device, frozen=False) -> torch.Tensor:
+    """frozen: the frozen-field workspace of include/nnr_frozen.h (its own pool entries: the same cfg, a far smaller buffer); "sparse": the
+    one of include/nnr_frozen_sparse.h (the same planes and the live list behind them)."""
+    key = _cfg_key(cfg, device) + (("frozen", frozen) if frozen else ())
     pool = _ws_pool.setdefault(key, [])
     if pool:
         return pool.pop()
-    n = (L.load().nnr_frozen_workspace_floats if frozen else L.load().nnr_workspace_floats)(C.byref(cfg))
+    lib = L.load()
+    sizer = lib.nnr_frozen_sparse_workspace_floats if frozen == "sparse" else lib.nnr_frozen_workspace_floats if frozen else lib.nnr_workspace_floats
+    n = sizer(C.byref(cfg))
     if n == 0:
         raise RuntimeError("nnr: unsupported configuration (hidden_dim must be 128 or 256; num_points <= 1024 for training)")
     return torch.empty(n, dtype=torch.float32, device=device)
 
 
-def _give_workspace(cfg: L.Cfg, device, ws: torch.Tensor, frozen: bool = False):
-    pool = _ws_pool.setdefault(_cfg_key(cfg, device) + (("frozen",) if frozen else ()), [])
+def _give_workspace(cfg: L.Cfg, device, ws: torch.Tensor, frozen=False):
+    pool = _ws_pool.setdefault(_cfg_key(cfg, device) + (("frozen", frozen) if frozen else ()), [])
     if len(pool) < 2:
         pool.append(ws)
 
@@ -384,21 +387,131 @@ class _RenderRaysFrozen(torch.autograd.Function):
         return (d_o if need[0] else None, d_d if need[1] else None, d_v if need[2] else None, None, None, None, None)
 
 
-_frozen_state = threading.local()      # .on: inside nnr.frozen_field() on this thread
+def _grid_args(grid, dev, what):
+    """The grid of include/nnr_sparse.h as ctypes arguments: an object with lo, inv_step, dims and bits (model.geometry.OccupancyGrid)."""
+    nx, ny, nz = (int(n) for n in grid.dims)
+    bits = grid.bits
+    if bits.dtype != torch.int32 or bits.device != dev or not bits.is_contiguous() or bits.numel() != nz * ny * ((nx + 31) // 32):
+        raise ValueError("%s: grid.bits must be a contiguous int32 tensor of %d words on the rays' device; got %r %r on %s"
+                         % (what, nz * ny * ((nx + 31) // 32), tuple(bits.shape), bits.dtype, bits.device))
+    lo3 = (C.c_float * 3)(*[float(v) for v in grid.lo])
+    is3 = (C.c_float * 3)(*[float(v) for v in grid.inv_step])
+    d3 = (C.c_int32 * 3)(nx, ny, nz)
+    return lo3, is3, d3, bits
+
+
+def _frozen_sparse_fwd(cfg, pts_o, pts_d, view_d, z_lo, z_hi, jit, grid, packed, ws, debug=False):
+    """nnr_frozen_sparse_fwd on prepared tensors -> rgb, dist, alpha, z (and count, live, n_live under debug)."""
+    dev = pts_o.device
+    R, N = cfg.n_rays, cfg.n_samples
+    f32 = dict(dtype=torch.float32, device=dev)
+    lo3, is3, d3, bits = _grid_args(grid, dev, "render_frozen_sparse")
+    rgb, dist = torch.empty(R, 3, **f32), torch.empty(R, **f32)
+    alpha, zv = torch.empty(R, N, **f32), torch.empty(R, N, **f32)
+    count = live = n_live = None
+    if debug:
+        count = torch.empty(R, dtype=torch.int32, device=dev)
+        live = torch.full((R * N,), -1, dtype=torch.int32, device=dev)
+        n_live = torch.empty(1, dtype=torch.int32, device=dev)
+    L.check(L.load().nnr_frozen_sparse_fwd(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(view_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), lo3, is3,
+                                           d3, L.ptr(bits), L.ptr(packed), L.ptr(rgb), L.ptr(dist), L.ptr(alpha), L.ptr(zv), L.ptr(count),
+                                           L.ptr(live), L.ptr(n_live), L.ptr(ws), L.stream()), "nnr_frozen_sparse_fwd")
+    return (rgb, dist, alpha, zv) + ((count, live, n_live) if debug else ())
+
+
+frozen_sparse_tally = None      # tools: while this is a list, every sparse frozen forward of the operator appends (n_live (1) int32 tensor, R N)
+
+
+class _RenderRaysFrozenSparse(torch.autograd.Function):
+    """render_rays(frozen=True, occupancy=grid) where the frozen kernels apply: nnr_frozen_sparse_fwd / nnr_frozen_sparse_bwd
+    (include/nnr_frozen_sparse.h).  As _RenderRaysFrozen: a node over the rays alone, the parameters get no .grad.  The grid is the caller's
+    object, valid because the caller says the field is frozen: it is never rebuilt or invalidated here."""
+
+    @staticmethod
+    def forward(ctx, pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts):
+        _require_gpu(pts_o)
+        dev = pts_o.device
+        R, N = pts_o.shape[0], z_lo.shape[0]
+        cfg = L.make_cfg(R, N, opts["hidden"], dist_alpha=opts["dist_alpha"], white_bg=opts["white_bg"], relu_sigma=opts["relu_sigma"], train=True)
+        pts_o, pts_d, view_d = (t.detach().contiguous().float() for t in (pts_o, pts_d, view_d))
+        z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
+        jit = jitter.detach().contiguous().float().view(R, N) if jitter is not None else None
+        packed = _packed_for(cfg, *opts["params"])
+        ws = _take_workspace(cfg, dev, frozen="sparse")
+        tally = frozen_sparse_tally
+        res = _frozen_sparse_fwd(cfg, pts_o, pts_d, view_d, z_lo, z_hi, jit, opts["occupancy"], packed, ws, debug=tally is not None)
+        rgb, dist, alpha, zv = res[:4]
+        if tally is not None:
+            tally.append((res[6], R * N))      # (no synchronisation here: the reader sums the tensors afterwards)
+        ctx.cfg, ctx.ws, ctx.packed, ctx.dev = cfg, ws, packed, dev
+        ctx.mark_non_differentiable(alpha, zv)
+        ctx.set_materialize_grads(False)
+        return rgb, dist, alpha, zv
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_dist, _da, _dz):
+        cfg, ws, dev = ctx.cfg, ctx.ws, ctx.dev
+        if ws is None:
+            raise RuntimeError("nnr: backward called twice on the same render (workspace already released)")
+        R = cfg.n_rays
+        f32 = dict(dtype=torch.float32, device=dev)
+        d_rgb = (d_rgb if d_rgb is not None else torch.zeros(R, 3, **f32)).contiguous().float()
+        d_dist = (d_dist if d_dist is not None else torch.zeros(R, **f32)).contiguous().float()
+        d_o, d_d, d_v = (torch.empty(R, 3, **f32) for _ in range(3))
+        L.check(L.load().nnr_frozen_sparse_bwd(C.byref(cfg), L.ptr(ctx.packed), L.ptr(d_rgb), L.ptr(d_dist), L.ptr(d_o), L.ptr(d_d), L.ptr(d_v),
+                                               L.ptr(ws), L.stream()), "nnr_frozen_sparse_bwd")
+        ctx.ws = None
+        _give_workspace(cfg, dev, ws, frozen="sparse")
+        need = ctx.needs_input_grad
+        return (d_o if need[0] else None, d_d if need[1] else None, d_v if need[2] else None, None, None, None, None)
+
+
+def render_frozen_sparse(pts_o, pts_d, view_d, z_lo, z_hi, jitter, grid, weights, biases, *, hidden: int, dist_alpha: bool, white_bg: bool,
+                         relu_sigma: bool, d_rgb=None, d_dist=None, debug: bool = False):
+    """The sparse frozen-field render on plain tensors, no autograd (tests and tools; refinement goes through render_rays(frozen=True,
+    occupancy=grid)): forward, and -- with d_rgb (R,3) and d_dist (R) -- backward.  Returns a dict: rgb, dist, alpha, z; d_pts_o, d_pts_d,
+    d_view where the backward ran; count (R) int32, live (R N) int32 (-1 behind the list) and n_live (1) int32 under debug."""
+    _require_gpu(pts_o)
+    dev = pts_o.device
+    R, N = pts_o.shape[0], z_lo.shape[0]
+    cfg = split2_cfg(R, N, hidden, dist_alpha=dist_alpha, relu_sigma=relu_sigma, train=True)
+    if white_bg:
+        cfg.flags |= L.NNR_F_WHITE_BG
+    pts_o, pts_d, view_d = (t.detach().contiguous().float() for t in (pts_o, pts_d, view_d))
+    z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
+    jit = jitter.detach().contiguous().float().view(R, N) if jitter is not None else None
+    packed = _packed_for(cfg, list(weights), list(biases))
+    ws = _take_workspace(cfg, dev, frozen="sparse")
+    res = _frozen_sparse_fwd(cfg, pts_o, pts_d, view_d, z_lo, z_hi, jit, grid, packed, ws, debug=debug)
+    out = dict(zip(("rgb", "dist", "alpha", "z", "count", "live", "n_live"), res))
+    if d_rgb is not None:
+        f32 = dict(dtype=torch.float32, device=dev)
+        d_rgb, d_dist = d_rgb.contiguous().float(), (d_dist if d_dist is not None else torch.zeros(R, **f32)).contiguous().float()
+        for k in ("d_pts_o", "d_pts_d", "d_view"):
+            out[k] = torch.empty(R, 3, **f32)
+        L.check(L.load().nnr_frozen_sparse_bwd(C.byref(cfg), L.ptr(packed), L.ptr(d_rgb), L.ptr(d_dist), L.ptr(out["d_pts_o"]), L.ptr(out["d_pts_d"]),
+                                               L.ptr(out["d_view"]), L.ptr(ws), L.stream()), "nnr_frozen_sparse_bwd")
+    _give_workspace(cfg, dev, ws, frozen="sparse")
+    return out
+
+
+_frozen_state = threading.local()      # .on: inside nnr.frozen_field() on this thread; .grid: its occupancy grid, if it was given one
 _frozen_said = set()                   # the reasons already logged: one line each per process
 _log = logging.getLogger("nnr")
 
 
 @contextlib.contextmanager
-def frozen_field():
+def frozen_field(occupancy=None):
     """Inside the block, on this thread, every render_rays call with frozen=None behaves as frozen=True: the field's weights and biases are
-    constants, the rays are differentiated (test-time pose refinement: model.Trainer_pose).  Nests; restores the previous state on exit."""
-    prev = getattr(_frozen_state, "on", False)
-    _frozen_state.on = True
+    constants, the rays are differentiated (test-time pose refinement: model.Trainer_pose).  Nests; restores the previous state on exit.
+    occupancy (default None): an occupancy grid of the field (model.geometry.OccupancyGrid, as render_sparse takes it); those calls then
+    behave as render_rays(frozen=True, occupancy=grid).  The grid is the caller's: valid because the caller says the field is frozen."""
+    prev = getattr(_frozen_state, "on", False), getattr(_frozen_state, "grid", None)
+    _frozen_state.on, _frozen_state.grid = True, occupancy
     try:
         yield
     finally:
-        _frozen_state.on = prev
+        _frozen_state.on, _frozen_state.grid = prev
 
 
 def _frozen_fallback_reason(pts_o, pts_d, view_d, bf16):
@@ -418,7 +531,7 @@ def _frozen_fallback_reason(pts_o, pts_d, view_d, bf16):
 def render_rays(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor,
                 jitter: Optional[torch.Tensor], weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor], *,
                 hidden: int, dist_alpha: bool, white_bg: bool, relu_sigma: bool, bf16: bool = False, samples: bool = True,
-                ray_distortion=None, frozen: Optional[bool] = None):
+                ray_distortion=None, frozen: Optional[bool] = None, occupancy=None):
     """(R,3) sampling origin / direction / view direction, (N) z interval tables, optional (R,N) jitter, the 12
     nn.Linear weights and biases in state_dict order  ->  rgb (R,3), dist (R), alpha (R,N), z (R,N).
     Differentiable w.r.t. pts_o, pts_d, view_d, weights, biases.  bf16: bf16-MFMA products (fp32 accumulation) in the MLP
@@ -432,9 +545,19 @@ def render_rays(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor, 
     kernels on the frozen workspace (include/nnr_frozen.h: no activation stash, no weight gradient, a workspace some 24 times smaller at
     hidden 256).  Where those do not apply (bf16=True, NNR_FP32_PRODUCTS other than split2, gradients disabled, no ray input that requires a
     gradient) today's kernels run with the weights detached, and one logged line (logger "nnr") says why.  Never inferred from requires_grad.
-    frozen=True with ray_distortion raises ValueError: the regulariser is a training term."""
+    frozen=True with ray_distortion raises ValueError: the regulariser is a training term.
+    occupancy=grid (default None, or the grid of the enclosing nnr.frozen_field(occupancy=grid) where frozen is None; only with a frozen
+    call, ValueError otherwise): an occupancy grid of the field (model.geometry.OccupancyGrid).  The frozen render then skips the samples in
+    cells the grid calls empty, forward and backward (include/nnr_frozen_sparse.h): the render of a field whose culled
+    samples hold no matter.  The grid is the caller's object and is never rebuilt or invalidated here.  Where the frozen kernels do not
+    apply the grid is ignored, the dense path runs, and one logged line per reason says so."""
     if frozen is None:
         frozen = getattr(_frozen_state, "on", False)
+        if frozen and occupancy is None:
+            occupancy = getattr(_frozen_state, "grid", None)
+    if occupancy is not None and not frozen:
+        raise ValueError("nnr: render_rays(occupancy=grid) needs frozen=True (or nnr.frozen_field): the grid is only valid for a field that "
+                         "does not move")
     if frozen and ray_distortion is not None:
         raise ValueError("nnr: render_rays(frozen=True) takes no ray_distortion: the regulariser is a term of the field's training")
     opts = dict(hidden=hidden, dist_alpha=dist_alpha, white_bg=white_bg, relu_sigma=relu_sigma, bf16=bool(bf16), samples=bool(samples),
@@ -444,10 +567,14 @@ def render_rays(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor, 
     if frozen:
         why = _frozen_fallback_reason(pts_o, pts_d, view_d, bool(bf16))
         if why is None:
+            if occupancy is not None:
+                opts["occupancy"] = occupancy
+                return _RenderRaysFrozenSparse.apply(pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts)
             return _RenderRaysFrozen.apply(pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts)
-        if why not in _frozen_said:
-            _frozen_said.add(why)
-            _log.info("nnr: render_rays(frozen=True) runs the training kernels with detached weights: %s", why)
+        said = why if occupancy is None else why + " (the occupancy grid is ignored: every sample is rendered)"
+        if said not in _frozen_said:
+            _frozen_said.add(said)
+            _log.info("nnr: render_rays(frozen=True) runs the training kernels with detached weights: %s", said)
         weights, biases = [w.detach() for w in weights], [b.detach() for b in biases]      # (opts["params"] keeps the caller's objects: the pack cache's key)
     if not torch.is_grad_enabled():
         # forward-only (eval / visualisation inside torch.no_grad): no stash, small workspace

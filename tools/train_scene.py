@@ -108,12 +108,15 @@ def pose_errors(pose_net, gt_poses, n_views):
     return {"ate": float(compute_ATE(gt, aligned)), "rpe_trans_x100": float(rpe_t * 100), "rpe_rot_deg": float(np.degrees(rpe_r))}
 
 
-def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_points=1024, frozen_field=True):
+def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_points=1024, frozen_field=True, frozen_occupancy=None):
     """What reference evaluation/eval.py:54-186 does for the held-out views: initialise their poses from the learned training
     trajectory (init_method 'pre': the training pose just before each held-out frame), optimise them against the frozen field
     (Trainer_pose, Adam 1e-3 halved five times), then render every held-out frame in full and score it.  LPIPS needs a VGG
     checkpoint and is reported as 0.  frozen_field (eval_pose.frozen_field; --no-frozen-eval: False): the refinement steps run the render
-    operator's frozen-field mode -- same losses and poses, no weight gradient; the path taken is printed."""
+    operator's frozen-field mode -- same losses and poses, no weight gradient; the path taken is printed.
+    frozen_occupancy = (resolution, alpha_min) (--frozen-occupancy; eval_pose.occupancy: true): the same refinement is run a second time from
+    the same initial poses with an occupancy grid of the field, built once, the samples it calls empty skipped forward and backward
+    (DESIGN.md section 15); the result carries the culled share, the largest distance between the two runs' refined poses and both PSNRs."""
     import dataloading as dl
     import model as mdl
     from model.eval_images import Eval_Images
@@ -125,33 +128,57 @@ def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_poi
         learned = torch.stack([pose(i) for i in range(train_field.N_imgs)])
     sr = train_field.sample_rate
     init = learned[int(sr / 2) - 1::sr - 1][:f.N_imgs].clone()
-    eval_pose = mdl.LearnPose(f.N_imgs, True, True, cfg, init_c2w=init).to(device)
-    opt = torch.optim.Adam(eval_pose.parameters(), lr=1e-3)
-    sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=list(range(0, epochs, max(1, epochs // 5))), gamma=0.5)
-    tp = mdl.Trainer_pose(nope, {"n_points": n_points, "type": "nope_nerf", "frozen_field": bool(frozen_field)}, device=device,
-                          optimizer_pose=opt, pose_param_net=eval_pose)
-    print(json.dumps({"eval_pose_path": "frozen field (nnr.frozen_field: no activation stash, no weight gradient)" if tp.frozen_field
-                      else "full training path (eval_pose.frozen_field: false)"}), flush=True)
-    first = last = None
-    for e in range(epochs):
-        l2 = torch.stack([tp.train_step(batch)["loss"].detach() for batch in loader]).mean()
-        sched.step()
-        if e in (0, epochs - 1):
-            v = float(l2)
-            first, last = (v, last) if e == 0 else (first, v)
-    eval_pose.eval()
-    with torch.no_grad():
-        c2ws = torch.stack([eval_pose(i) for i in range(f.N_imgs)])
-    cfg = dict(cfg, extract_images={"resolution": [f.H, f.W]})
-    gen = Eval_Images(nope.renderer, cfg, use_learnt_poses=True, use_learnt_focal=False, device=device, render_type="nope_nerf",
-                      c2ws=c2ws, img_list=f.img_list)
     zero = lambda a, b, normalize=True: torch.zeros(())
-    t0 = time.perf_counter()
-    rows = [gen.eval_images(batch, out_dir, None, zero, logger=None) for batch in loader]
-    dt = time.perf_counter() - t0
-    return {"views": f.N_imgs, "pose_opt_epochs": epochs, "pose_opt_mse_first": first, "pose_opt_mse_last": last,
-            "psnr": float(np.mean([r["psnr"] for r in rows])), "ssim": float(np.mean([r["ssim"] for r in rows])),
-            "seconds_per_frame": dt / max(1, len(rows))}
+
+    def refine_and_score(occupancy):
+        eval_pose = mdl.LearnPose(f.N_imgs, True, True, cfg, init_c2w=init.clone()).to(device)
+        opt = torch.optim.Adam(eval_pose.parameters(), lr=1e-3)
+        sched = torch.optim.lr_scheduler.MultiStepLR(opt, milestones=list(range(0, epochs, max(1, epochs // 5))), gamma=0.5)
+        tp = mdl.Trainer_pose(nope, {"n_points": n_points, "type": "nope_nerf", "frozen_field": bool(frozen_field), "occupancy": bool(occupancy)},
+                              device=device, optimizer_pose=opt, pose_param_net=eval_pose)
+        print(json.dumps({"eval_pose_path": ("frozen field with an occupancy grid (nnr.frozen_field(occupancy=grid): known-empty samples skipped)"
+                                             if tp.occupancy else "frozen field (nnr.frozen_field: no activation stash, no weight gradient)")
+                          if tp.frozen_field else "full training path (eval_pose.frozen_field: false)"}), flush=True)
+        first = last = None
+        from nnr import ops
+        ops.frozen_sparse_tally = [] if occupancy else None
+        try:
+            if occupancy:      # (the key is the renderer's; it is taken away again before the frames are rendered: those stay dense)
+                nope.renderer.cfg["occupancy"] = {"resolution": int(frozen_occupancy[0]), "alpha_min": float(frozen_occupancy[1])}
+            for e in range(epochs):
+                l2 = torch.stack([tp.train_step(batch)["loss"].detach() for batch in loader]).mean()
+                sched.step()
+                if e in (0, epochs - 1):
+                    v = float(l2)
+                    first, last = (v, last) if e == 0 else (first, v)
+        finally:
+            tally, ops.frozen_sparse_tally = ops.frozen_sparse_tally, None
+            if occupancy:
+                nope.renderer.cfg.pop("occupancy", None)
+        eval_pose.eval()
+        with torch.no_grad():
+            c2ws = torch.stack([eval_pose(i) for i in range(f.N_imgs)])
+        gen = Eval_Images(nope.renderer, dict(cfg, extract_images={"resolution": [f.H, f.W]}), use_learnt_poses=True, use_learnt_focal=False,
+                          device=device, render_type="nope_nerf", c2ws=c2ws, img_list=f.img_list)
+        t0 = time.perf_counter()
+        rows = [gen.eval_images(batch, out_dir, None, zero, logger=None) for batch in loader]
+        dt = time.perf_counter() - t0
+        res = {"views": f.N_imgs, "pose_opt_epochs": epochs, "pose_opt_mse_first": first, "pose_opt_mse_last": last,
+               "psnr": float(np.mean([r["psnr"] for r in rows])), "ssim": float(np.mean([r["ssim"] for r in rows])),
+               "seconds_per_frame": dt / max(1, len(rows))}
+        if tally:
+            live, total = float(torch.stack([t[0] for t in tally]).sum()), float(sum(t[1] for t in tally))
+            res.update(samples_culled=1. - live / total, grid_builds=tp.occupancy_builds,
+                       cells_occupied=float(tp.occupancy_grid.occupied) if tp.occupancy_grid is not None else None)
+        return res, c2ws
+
+    dense, c2ws = refine_and_score(False)
+    if frozen_occupancy is None or not frozen_field:
+        return dense
+    sparse, c2ws_s = refine_and_score(True)
+    sparse["pose_distance_to_dense"] = {"rotation_max_abs": float((c2ws_s[:, :3, :3] - c2ws[:, :3, :3]).abs().max()),
+                                        "translation_max_abs": float((c2ws_s[:, :3, 3] - c2ws[:, :3, 3]).abs().max())}
+    return dict(dense, frozen_occupancy=sparse)
 
 
 def occupancy_compare(cfg, nope, pose, loader, field, device, resolution, alpha_mins, dilate=1, bounds=None, frames=4):
@@ -221,7 +248,7 @@ def occupancy_compare(cfg, nope, pose, loader, field, device, resolution, alpha_
 
 
 def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=None, eval_epochs=0, eval_dir=None, checkpoint_dir=None,
-        occupancy=None, frozen_eval=True, **cfg_kw):
+        occupancy=None, frozen_eval=True, frozen_occupancy=None, **cfg_kw):
     """-> dict with the per-epoch PSNR / pose-error curve and the loop throughput (+ novel-view scores with eval_epochs > 0)."""
     import dataloading as dl
     from model.common import mse2psnr
@@ -272,7 +299,7 @@ def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=No
         import tempfile
         with tempfile.TemporaryDirectory() as tmp:
             novel = novel_view_eval(cfg, trainer.model, pose, field, device, eval_epochs, eval_dir or tmp, n_points=min(1024, n_rays),
-                                    frozen_field=frozen_eval)
+                                    frozen_field=frozen_eval, frozen_occupancy=frozen_occupancy)
     occ_rows = None
     if occupancy is not None:      # (resolution, [alpha_min, ...]): dense against sparse evaluation frames
         if num_fine_of(cfg):
@@ -313,6 +340,9 @@ def main():
     ap.add_argument("--eval-epochs", type=int, default=0, help="test-time pose optimisation epochs before scoring the held-out views")
     ap.add_argument("--no-frozen-eval", action="store_true",
                     help="eval_pose.frozen_field: false -- refine the held-out views' poses on the operator's full training path instead of its frozen-field mode")
+    ap.add_argument("--frozen-occupancy", nargs=2, default=None, metavar=("RES", "ALPHA_MIN"),
+                    help="eval_pose.occupancy: true -- refine the held-out poses a second time with an occupancy grid {resolution: RES, alpha_min: "
+                         "ALPHA_MIN} of the frozen field, built once; prints the path taken, the culled share and both runs' poses and PSNR")
     ap.add_argument("--eval-dir", default=None, help="where the rendered held-out frames go (default: a temporary directory)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--checkpoint-dir", default=None, help="write model.pt, model_pose.pt and config.yaml here after the last epoch (tools/extract_mesh.py takes DIR/config.yaml)")
@@ -323,7 +353,8 @@ def main():
     res = run(a.path, a.scene, style=a.style, epochs=a.epochs, log_every=a.log_every, eval_epochs=a.eval_epochs, eval_dir=a.eval_dir, checkpoint_dir=a.checkpoint_dir, n_rays=a.rays, n_samples=a.samples,
               hidden=a.hidden, resident=not a.host_loader, aux=not a.no_aux, resize_factor=a.factor, workers=a.workers,
               mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine, proposal=a.proposal, occupancy=occupancy,
-              ray_distortion=a.ray_distortion, frozen_eval=not a.no_frozen_eval)
+              ray_distortion=a.ray_distortion, frozen_eval=not a.no_frozen_eval,
+              frozen_occupancy=None if a.frozen_occupancy is None else (int(a.frozen_occupancy[0]), float(a.frozen_occupancy[1])))
     print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
