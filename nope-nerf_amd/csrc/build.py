@@ -32,7 +32,8 @@ SOURCES = [("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MOD
            ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256",)), ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=128",)),
            ("nnr_mlp_fwd_bf16.hip", ()), ("nnr_mlp_dgrad_bf16.hip", ()), ("nnr_mlp_fwd.hip", ()), ("nnr_mlp_dgrad.hip", ()), ("nnr_depth_f16.hip", ()),
-           ("nnr_api.cpp", ()), ("nnr_wgrad_plan.cpp", ()), ("nnr_fusion_api.cpp", ()), ("nnr_sparse_api.cpp", ()), ("nnr_regularise_api.cpp", ()), ("nnr_tsdf.hip", ()), ("nnr_pack.hip", ()), ("nnr_wgrad_bf16.hip", ()), ("nnr_composite.hip", ()), ("nnr_ray_distortion.hip", ()), ("nnr_resample.hip", ()),
+           ("nnr_api.cpp", ()), ("nnr_wgrad_plan.cpp", ()), ("nnr_fusion_api.cpp", ()), ("nnr_sparse_api.cpp", ()), ("nnr_frozen_api.cpp", ()), ("nnr_regularise_api.cpp", ()), ("nnr_tsdf.hip", ()),
+           ("nnr_frozen_sparse.hip", ()), ("nnr_pack.hip", ()), ("nnr_wgrad_bf16.hip", ()), ("nnr_composite.hip", ()), ("nnr_ray_distortion.hip", ()), ("nnr_resample.hip", ()),
            ("nnr_camera.hip", ()), ("nnr_pointcloud.hip", ()), ("nnr_aux.hip", ()), ("nnr_randperm.hip", ()), ("nnr_optim.hip", ())]
 
 
@@ -61,6 +62,7 @@ SCRATCH_LIMIT = {"18mlp_fwd_f16_kernelI": 0, "18mlp_fwd_f16_kernelILi256ELb0E": 
                  "16march_f16_kernelI": 0, "19march_finish_kernel": 0, "15resample_kernelE": 0, "18propose_f16_kernelI": 0, "15grid_f16_kernelI": 0, "17bricks_f16_kernelI": 0,
                  "16depth_f16_kernelI": 0, "21tsdf_integrate_kernelE": 0,
                  "25ray_distortion_fwd_kernelE": 0, "25ray_distortion_bwd_kernelE": 0,
+                 "25frozen_sparse_flag_kernelE": 0, "25frozen_sparse_scan_kernelE": 0, "25frozen_sparse_fill_kernelE": 0,      # (the compaction: nnr_frozen_sparse.hip)
                  "17sparse_f16_kernelI": 48}      # (the inference forward's passes and composite carry: its allowance)
 
 

@@ -755,8 +755,3 @@ int nnr_aux_terms_bwd(const nnr_aux_cfg* cfg, const float* d1_img, const float* 
 }
 
 }  // extern "C"
-
-// the frozen-field entry points (include/nnr_frozen.h), part of this unit: see the file's header
-#include "nnr_frozen_api.cpp"
-// the sparse frozen-field entry points and their compaction kernels (include/nnr_frozen_sparse.h), likewise
-#include "nnr_frozen_sparse_api.cpp"

@@ -12,7 +12,7 @@
 //     again: the ray's exclusive offset, and n_live behind the last.  Integer sums: any order gives the same numbers.
 //   * fill: one wave per ray again, lane l of round k holds bit l of the mask's words 2 k, 2 k + 1: live[offset + popcount of the bits
 //     below] = ray * N + j.
-// Plain vector loads and stores only.  Compiled with its entry points: nnr_frozen_sparse_api.cpp includes this file (no unit of its own).
+// Plain vector loads and stores only.  A unit of its own (csrc/build.py); its one launcher is called from nnr_frozen_api.cpp.
 #include "nnr_device.h"
 #include "nnr_frozen_sparse_kernels.h"
 #include "nnr_sparse_cell.h"
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void frozen_sparse_fill_kernel(FrozenSparseArg
     if (ray >= a.R) return;
     const int N = a.N;
     const uint32_t* const mask = a.ray_mask + (int64_t)ray * kFrozenSparseMaskWords;
-    const int row0 = ray * N;      // (S <= 2^31 - 1: nnr_frozen_sparse_api.cpp)
+    const int row0 = ray * N;      // (S <= 2^31 - 1: nnr_frozen_api.cpp)
     int pos = a.ray_off[ray];
     for (int k = 0; 64 * k < N; ++k) {
         const uint64_t m = (uint64_t)mask[2 * k] | ((uint64_t)mask[2 * k + 1] << 32);

@@ -55,7 +55,7 @@ struct FrozenSparseArgs {
 };
 constexpr int kFrozenSparseMaskWords = 32;      // N <= 1024
 
-hipError_t launch_frozen_sparse_compact(const FrozenSparseArgs& a, hipStream_t st);      // nnr_frozen_sparse.hip (in nnr_api.cpp's unit): three launches
+hipError_t launch_frozen_sparse_compact(const FrozenSparseArgs& a, hipStream_t st);      // nnr_frozen_sparse.hip: three launches
 
 template <int D> hipError_t launch_mlp_fwd_frozen_list_variant(const MlpFwdListArgs& a, hipStream_t st);       // one translation unit each (csrc/build.py)
 template <int D> hipError_t launch_mlp_dgrad_frozen_list_variant(const MlpDgradListArgs& a, hipStream_t st);

@@ -4,10 +4,10 @@
 // the caller's stream.  No state: the last HIP error is nnr_api.cpp's (launched).
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdint>
 
 #include "../../include/nnr_sparse.h"
+#include "nnr_grid_check.h"
 #include "nnr_sparse_kernels.h"
 
 using namespace nnr;
@@ -27,15 +27,12 @@ int nnr_render_sparse(const nnr_cfg* cfg, const float* pts_o, const float* pts_d
     if (!cfg || cfg->n_rays < 1 || cfg->n_samples < 1) return NNR_E_BADCFG;
     if (!pts_o || !pts_d || !view_d || !z_lo || !z_hi || !grid_lo || !grid_inv_step || !grid_dims || !bits || !packed || !out)
         return NNR_E_BADCFG;      // (jitter and the opt_* may be null)
-    for (int c = 0; c < 3; ++c) {
-        if (grid_dims[c] < 1) return NNR_E_BADCFG;
-        if (!std::isfinite(grid_lo[c]) || !std::isfinite(grid_inv_step[c]) || !(grid_inv_step[c] > 0.f)) return NNR_E_BADCFG;
-    }
+    int64_t wx;
+    const int grid_rc = check_grid(grid_lo, grid_inv_step, grid_dims, &wx);
+    if (grid_rc == NNR_E_BADCFG) return grid_rc;      // (a bad grid is refused before an unsupported cfg, an unsupported grid behind it)
     if (cfg->n_samples > 256 || (cfg->hidden != 128 && cfg->hidden != 256)) return NNR_E_UNSUPPORTED;
     if ((cfg->flags & (NNR_F_BF16 | NNR_F_SPLIT3 | NNR_F_SPLIT2)) != (NNR_F_SPLIT3 | NNR_F_SPLIT2) || (cfg->flags & NNR_F_TRAIN)) return NNR_E_UNSUPPORTED;
-    const int64_t wx = ((int64_t)grid_dims[0] + 31) / 32;
-    const int64_t rows = (int64_t)grid_dims[2] * grid_dims[1];      // < 2^62
-    if (rows > INT32_MAX || rows * wx > INT32_MAX || rows * grid_dims[0] > INT32_MAX) return NNR_E_UNSUPPORTED;
+    if (grid_rc != NNR_OK) return grid_rc;
     if (!aligned(packed, 16)) return NNR_E_ALIGN;
     for (const void* p : {(const void*)pts_o, (const void*)pts_d, (const void*)view_d, (const void*)z_lo, (const void*)z_hi, (const void*)jitter,
                           (const void*)bits, (const void*)out, (const void*)opt_count, (const void*)opt_cell, (const void*)opt_out4})

@@ -106,23 +106,27 @@ def _cfg_key(cfg: L.Cfg, device):
     return (str(device), cfg.n_rays, cfg.n_samples, cfg.hidden, cfg.flags)
 
 
-def _take_workspace(cfg: L.Cfg, device, frozen=False) -> torch.Tensor:
-    """frozen: the frozen-field workspace of include/nnr_frozen.h (its own pool entries: the same cfg, a far smaller buffer); "sparse": the
-    one of include/nnr_frozen_sparse.h (the same planes and the live list behind them)."""
-    key = _cfg_key(cfg, device) + (("frozen", frozen) if frozen else ())
-    pool = _ws_pool.setdefault(key, [])
+_WS_SIZER = {None: "nnr_workspace_floats", "frozen": "nnr_frozen_workspace_floats", "frozen_sparse": "nnr_frozen_sparse_workspace_floats"}
+
+
+def _ws_pool_of(cfg: L.Cfg, device, kind):
+    return _ws_pool.setdefault(_cfg_key(cfg, device) + ((kind,) if kind else ()), [])
+
+
+def _take_workspace(cfg: L.Cfg, device, kind=None) -> torch.Tensor:
+    """kind: None, the workspace of include/nnr.h; "frozen", the frozen-field workspace of include/nnr_frozen.h (the same cfg, a far smaller
+    buffer); "frozen_sparse", the one of include/nnr_frozen_sparse.h (the same planes and the live list behind them).  A pool per kind."""
+    pool = _ws_pool_of(cfg, device, kind)
     if pool:
         return pool.pop()
-    lib = L.load()
-    sizer = lib.nnr_frozen_sparse_workspace_floats if frozen == "sparse" else lib.nnr_frozen_workspace_floats if frozen else lib.nnr_workspace_floats
-    n = sizer(C.byref(cfg))
+    n = getattr(L.load(), _WS_SIZER[kind])(C.byref(cfg))
     if n == 0:
         raise RuntimeError("nnr: unsupported configuration (hidden_dim must be 128 or 256; num_points <= 1024 for training)")
     return torch.empty(n, dtype=torch.float32, device=device)
 
 
-def _give_workspace(cfg: L.Cfg, device, ws: torch.Tensor, frozen=False):
-    pool = _ws_pool.setdefault(_cfg_key(cfg, device) + (("frozen", frozen) if frozen else ()), [])
+def _give_workspace(cfg: L.Cfg, device, ws: torch.Tensor, kind=None):
+    pool = _ws_pool_of(cfg, device, kind)
     if len(pool) < 2:
         pool.append(ws)
 
@@ -206,6 +210,15 @@ def workspace_plane(cfg: L.Cfg, ws: torch.Tensor, plane: int, n_rows: Optional[i
 # ----------------------------------------------------------------------------------------------------------------------
 # the operator
 # ----------------------------------------------------------------------------------------------------------------------
+def _ray_inputs(rays, z_lo, z_hi, jitter):
+    """What every render entry point reads of its rays: the (R,3) tensors `rays`, the two (N) z tables and the jitter -- (R,N), or None,
+    which stays None -- detached, contiguous and fp32.  -> (list of rays, z_lo, z_hi, jitter)"""
+    R, N = rays[0].shape[0], z_lo.shape[0]
+    rays = [t.detach().contiguous().float() for t in rays]
+    z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
+    return rays, z_lo, z_hi, (jitter.detach().contiguous().float().view(R, N) if jitter is not None else None)
+
+
 class _RenderRays(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts, *params):
@@ -218,9 +231,7 @@ class _RenderRays(torch.autograd.Function):
                          relu_sigma=opts["relu_sigma"], train=need_grad, bf16=opts.get("bf16", False))
         lib = L.load()
         f32 = dict(dtype=torch.float32, device=dev)
-        pts_o, pts_d, view_d = (t.detach().contiguous().float() for t in (pts_o, pts_d, view_d))
-        z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
-        jit = jitter.detach().contiguous().float().view(R, N) if jitter is not None else None
+        (pts_o, pts_d, view_d), z_lo, z_hi, jit = _ray_inputs((pts_o, pts_d, view_d), z_lo, z_hi, jitter)
         packed = _packed_for(cfg, *opts["params"])
         ws = _take_workspace(cfg, dev)
         rgb = torch.empty(R, 3, **f32)
@@ -343,50 +354,6 @@ def flat_grads_of(storage_ptr: int):
 # ----------------------------------------------------------------------------------------------------------------------
 # the frozen-field operator (include/nnr_frozen.h): the rays are differentiated, the field is a constant
 # ----------------------------------------------------------------------------------------------------------------------
-class _RenderRaysFrozen(torch.autograd.Function):
-    """render_rays(frozen=True) where the frozen kernels apply: nnr_frozen_fwd / nnr_frozen_bwd on the frozen workspace.  The parameters are
-    not inputs of the node (they reach it through opts, for the pack cache): autograd has no edge to them, their .grad stay None."""
-
-    @staticmethod
-    def forward(ctx, pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts):
-        _require_gpu(pts_o)
-        dev = pts_o.device
-        R, N = pts_o.shape[0], z_lo.shape[0]
-        cfg = L.make_cfg(R, N, opts["hidden"], dist_alpha=opts["dist_alpha"], white_bg=opts["white_bg"], relu_sigma=opts["relu_sigma"], train=True)
-        lib = L.load()
-        f32 = dict(dtype=torch.float32, device=dev)
-        pts_o, pts_d, view_d = (t.detach().contiguous().float() for t in (pts_o, pts_d, view_d))
-        z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
-        jit = jitter.detach().contiguous().float().view(R, N) if jitter is not None else None
-        packed = _packed_for(cfg, *opts["params"])
-        ws = _take_workspace(cfg, dev, frozen=True)
-        rgb, dist = torch.empty(R, 3, **f32), torch.empty(R, **f32)
-        alpha, zv = torch.empty(R, N, **f32), torch.empty(R, N, **f32)
-        L.check(lib.nnr_frozen_fwd(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(view_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), L.ptr(packed),
-                                   L.ptr(rgb), L.ptr(dist), L.ptr(alpha), L.ptr(zv), L.ptr(ws), L.stream()), "nnr_frozen_fwd")
-        ctx.cfg, ctx.ws, ctx.packed, ctx.dev = cfg, ws, packed, dev
-        ctx.mark_non_differentiable(alpha, zv)
-        ctx.set_materialize_grads(False)
-        return rgb, dist, alpha, zv
-
-    @staticmethod
-    def backward(ctx, d_rgb, d_dist, _da, _dz):
-        cfg, ws, dev = ctx.cfg, ctx.ws, ctx.dev
-        if ws is None:
-            raise RuntimeError("nnr: backward called twice on the same render (workspace already released)")
-        R = cfg.n_rays
-        f32 = dict(dtype=torch.float32, device=dev)
-        d_rgb = (d_rgb if d_rgb is not None else torch.zeros(R, 3, **f32)).contiguous().float()
-        d_dist = (d_dist if d_dist is not None else torch.zeros(R, **f32)).contiguous().float()
-        d_o, d_d, d_v = (torch.empty(R, 3, **f32) for _ in range(3))
-        L.check(L.load().nnr_frozen_bwd(C.byref(cfg), L.ptr(ctx.packed), L.ptr(d_rgb), L.ptr(d_dist), L.ptr(d_o), L.ptr(d_d), L.ptr(d_v),
-                                        L.ptr(ws), L.stream()), "nnr_frozen_bwd")
-        ctx.ws = None
-        _give_workspace(cfg, dev, ws, frozen=True)
-        need = ctx.needs_input_grad
-        return (d_o if need[0] else None, d_d if need[1] else None, d_v if need[2] else None, None, None, None, None)
-
-
 def _grid_args(grid, dev, what):
     """The grid of include/nnr_sparse.h as ctypes arguments: an object with lo, inv_step, dims and bits (model.geometry.OccupancyGrid)."""
     nx, ny, nz = (int(n) for n in grid.dims)
@@ -422,10 +389,25 @@ def _frozen_sparse_fwd(cfg, pts_o, pts_d, view_d, z_lo, z_hi, jit, grid, packed,
 frozen_sparse_tally = None      # tools: while this is a list, every sparse frozen forward of the operator appends (n_live (1) int32 tensor, R N)
 
 
-class _RenderRaysFrozenSparse(torch.autograd.Function):
-    """render_rays(frozen=True, occupancy=grid) where the frozen kernels apply: nnr_frozen_sparse_fwd / nnr_frozen_sparse_bwd
-    (include/nnr_frozen_sparse.h).  As _RenderRaysFrozen: a node over the rays alone, the parameters get no .grad.  The grid is the caller's
-    object, valid because the caller says the field is frozen: it is never rebuilt or invalidated here."""
+def _frozen_bwd(cfg, kind, packed, d_rgb, d_dist, ws):
+    """nnr_frozen_bwd or nnr_frozen_sparse_bwd, by the kind of workspace ("frozen" / "frozen_sparse") the forward filled -> d_pts_o, d_pts_d,
+    d_view, (R,3) each.  An upstream gradient that is None counts as zero."""
+    R = cfg.n_rays
+    f32 = dict(dtype=torch.float32, device=ws.device)
+    d_rgb = (d_rgb if d_rgb is not None else torch.zeros(R, 3, **f32)).contiguous().float()
+    d_dist = (d_dist if d_dist is not None else torch.zeros(R, **f32)).contiguous().float()
+    d_o, d_d, d_v = (torch.empty(R, 3, **f32) for _ in range(3))
+    name = "nnr_%s_bwd" % kind
+    L.check(getattr(L.load(), name)(C.byref(cfg), L.ptr(packed), L.ptr(d_rgb), L.ptr(d_dist), L.ptr(d_o), L.ptr(d_d), L.ptr(d_v), L.ptr(ws),
+                                    L.stream()), name)
+    return d_o, d_d, d_v
+
+
+class _RenderRaysFrozen(torch.autograd.Function):
+    """render_rays(frozen=True) where the frozen kernels apply: nnr_frozen_fwd / nnr_frozen_bwd on the frozen workspace, or -- with a grid in
+    opts["occupancy"] -- nnr_frozen_sparse_fwd / nnr_frozen_sparse_bwd on the sparse one (include/nnr_frozen_sparse.h).  The parameters are
+    not inputs of the node (they reach it through opts, for the pack cache): autograd has no edge to them, their .grad stay None.  The grid is
+    the caller's object, valid because the caller says the field is frozen: it is never rebuilt or invalidated here."""
 
     @staticmethod
     def forward(ctx, pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts):
@@ -433,35 +415,36 @@ class _RenderRaysFrozenSparse(torch.autograd.Function):
         dev = pts_o.device
         R, N = pts_o.shape[0], z_lo.shape[0]
         cfg = L.make_cfg(R, N, opts["hidden"], dist_alpha=opts["dist_alpha"], white_bg=opts["white_bg"], relu_sigma=opts["relu_sigma"], train=True)
-        pts_o, pts_d, view_d = (t.detach().contiguous().float() for t in (pts_o, pts_d, view_d))
-        z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
-        jit = jitter.detach().contiguous().float().view(R, N) if jitter is not None else None
+        (pts_o, pts_d, view_d), z_lo, z_hi, jit = _ray_inputs((pts_o, pts_d, view_d), z_lo, z_hi, jitter)
         packed = _packed_for(cfg, *opts["params"])
-        ws = _take_workspace(cfg, dev, frozen="sparse")
-        tally = frozen_sparse_tally
-        res = _frozen_sparse_fwd(cfg, pts_o, pts_d, view_d, z_lo, z_hi, jit, opts["occupancy"], packed, ws, debug=tally is not None)
-        rgb, dist, alpha, zv = res[:4]
-        if tally is not None:
-            tally.append((res[6], R * N))      # (no synchronisation here: the reader sums the tensors afterwards)
-        ctx.cfg, ctx.ws, ctx.packed, ctx.dev = cfg, ws, packed, dev
+        grid = opts.get("occupancy")
+        kind = "frozen" if grid is None else "frozen_sparse"
+        ws = _take_workspace(cfg, dev, kind)
+        if grid is None:
+            f32 = dict(dtype=torch.float32, device=dev)
+            rgb, dist = torch.empty(R, 3, **f32), torch.empty(R, **f32)
+            alpha, zv = torch.empty(R, N, **f32), torch.empty(R, N, **f32)
+            L.check(L.load().nnr_frozen_fwd(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(view_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit),
+                                            L.ptr(packed), L.ptr(rgb), L.ptr(dist), L.ptr(alpha), L.ptr(zv), L.ptr(ws), L.stream()), "nnr_frozen_fwd")
+        else:
+            tally = frozen_sparse_tally
+            res = _frozen_sparse_fwd(cfg, pts_o, pts_d, view_d, z_lo, z_hi, jit, grid, packed, ws, debug=tally is not None)
+            rgb, dist, alpha, zv = res[:4]
+            if tally is not None:
+                tally.append((res[6], R * N))      # (no synchronisation here: the reader sums the tensors afterwards)
+        ctx.cfg, ctx.ws, ctx.kind, ctx.packed, ctx.dev = cfg, ws, kind, packed, dev
         ctx.mark_non_differentiable(alpha, zv)
         ctx.set_materialize_grads(False)
         return rgb, dist, alpha, zv
 
     @staticmethod
     def backward(ctx, d_rgb, d_dist, _da, _dz):
-        cfg, ws, dev = ctx.cfg, ctx.ws, ctx.dev
+        cfg, ws = ctx.cfg, ctx.ws
         if ws is None:
             raise RuntimeError("nnr: backward called twice on the same render (workspace already released)")
-        R = cfg.n_rays
-        f32 = dict(dtype=torch.float32, device=dev)
-        d_rgb = (d_rgb if d_rgb is not None else torch.zeros(R, 3, **f32)).contiguous().float()
-        d_dist = (d_dist if d_dist is not None else torch.zeros(R, **f32)).contiguous().float()
-        d_o, d_d, d_v = (torch.empty(R, 3, **f32) for _ in range(3))
-        L.check(L.load().nnr_frozen_sparse_bwd(C.byref(cfg), L.ptr(ctx.packed), L.ptr(d_rgb), L.ptr(d_dist), L.ptr(d_o), L.ptr(d_d), L.ptr(d_v),
-                                               L.ptr(ws), L.stream()), "nnr_frozen_sparse_bwd")
+        d_o, d_d, d_v = _frozen_bwd(cfg, ctx.kind, ctx.packed, d_rgb, d_dist, ws)
         ctx.ws = None
-        _give_workspace(cfg, dev, ws, frozen="sparse")
+        _give_workspace(cfg, ctx.dev, ws, ctx.kind)      # to the pool of its own kind
         need = ctx.needs_input_grad
         return (d_o if need[0] else None, d_d if need[1] else None, d_v if need[2] else None, None, None, None, None)
 
@@ -477,21 +460,14 @@ def render_frozen_sparse(pts_o, pts_d, view_d, z_lo, z_hi, jitter, grid, weights
     cfg = split2_cfg(R, N, hidden, dist_alpha=dist_alpha, relu_sigma=relu_sigma, train=True)
     if white_bg:
         cfg.flags |= L.NNR_F_WHITE_BG
-    pts_o, pts_d, view_d = (t.detach().contiguous().float() for t in (pts_o, pts_d, view_d))
-    z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
-    jit = jitter.detach().contiguous().float().view(R, N) if jitter is not None else None
+    (pts_o, pts_d, view_d), z_lo, z_hi, jit = _ray_inputs((pts_o, pts_d, view_d), z_lo, z_hi, jitter)
     packed = _packed_for(cfg, list(weights), list(biases))
-    ws = _take_workspace(cfg, dev, frozen="sparse")
+    ws = _take_workspace(cfg, dev, "frozen_sparse")
     res = _frozen_sparse_fwd(cfg, pts_o, pts_d, view_d, z_lo, z_hi, jit, grid, packed, ws, debug=debug)
     out = dict(zip(("rgb", "dist", "alpha", "z", "count", "live", "n_live"), res))
     if d_rgb is not None:
-        f32 = dict(dtype=torch.float32, device=dev)
-        d_rgb, d_dist = d_rgb.contiguous().float(), (d_dist if d_dist is not None else torch.zeros(R, **f32)).contiguous().float()
-        for k in ("d_pts_o", "d_pts_d", "d_view"):
-            out[k] = torch.empty(R, 3, **f32)
-        L.check(L.load().nnr_frozen_sparse_bwd(C.byref(cfg), L.ptr(packed), L.ptr(d_rgb), L.ptr(d_dist), L.ptr(out["d_pts_o"]), L.ptr(out["d_pts_d"]),
-                                               L.ptr(out["d_view"]), L.ptr(ws), L.stream()), "nnr_frozen_sparse_bwd")
-    _give_workspace(cfg, dev, ws, frozen="sparse")
+        out["d_pts_o"], out["d_pts_d"], out["d_view"] = _frozen_bwd(cfg, "frozen_sparse", packed, d_rgb, d_dist, ws)
+    _give_workspace(cfg, dev, ws, "frozen_sparse")
     return out
 
 
@@ -567,9 +543,7 @@ def render_rays(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor, 
     if frozen:
         why = _frozen_fallback_reason(pts_o, pts_d, view_d, bool(bf16))
         if why is None:
-            if occupancy is not None:
-                opts["occupancy"] = occupancy
-                return _RenderRaysFrozenSparse.apply(pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts)
+            opts["occupancy"] = occupancy
             return _RenderRaysFrozen.apply(pts_o, pts_d, view_d, z_lo, z_hi, jitter, opts)
         said = why if occupancy is None else why + " (the occupancy grid is ignored: every sample is rendered)"
         if said not in _frozen_said:
@@ -753,9 +727,7 @@ def render_depth(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z
     R, Cn = pts_o.shape[0], z_lo.shape[0]
     dev = pts_o.device
     cfg = split2_cfg(R, Cn, hidden, dist_alpha=dist_alpha, relu_sigma=relu_sigma)
-    pts_o, pts_d = pts_o.detach().contiguous().float(), pts_d.detach().contiguous().float()
-    z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
-    jit = jitter.detach().contiguous().float().view(R, Cn) if jitter is not None else None
+    (pts_o, pts_d), z_lo, z_hi, jit = _ray_inputs((pts_o, pts_d), z_lo, z_hi, jitter)
     packed = _packed_for(cfg, list(weights), list(biases))
     f32 = dict(dtype=torch.float32, device=dev)
     out = torch.empty(R, 2, **f32)
@@ -778,17 +750,11 @@ def render_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor
     _require_gpu(pts_o)
     R, Cn = pts_o.shape[0], z_lo.shape[0]
     dev = pts_o.device
-    flags = L.NNR_F_SPLIT3 | L.NNR_F_SPLIT2 | (L.NNR_F_DIST_ALPHA if dist_alpha else 0) | (L.NNR_F_RELU_SIGMA if relu_sigma else 0) | \
-        (L.NNR_F_WHITE_BG if white_bg else 0)
-    cfg = L.Cfg(int(R), int(Cn), int(hidden), flags)
-    pts_o, pts_d, view_d = (t.detach().contiguous().float() for t in (pts_o, pts_d, view_d))
-    z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
-    jit = jitter.detach().contiguous().float().view(R, Cn) if jitter is not None else None
-    nx, ny, nz = (int(n) for n in grid.dims)
-    bits = grid.bits
-    if bits.dtype != torch.int32 or bits.device != dev or not bits.is_contiguous() or bits.numel() != nz * ny * ((nx + 31) // 32):
-        raise ValueError("render_sparse: grid.bits must be a contiguous int32 tensor of %d words on the rays' device; got %r %r on %s"
-                         % (nz * ny * ((nx + 31) // 32), tuple(bits.shape), bits.dtype, bits.device))
+    cfg = split2_cfg(R, Cn, hidden, dist_alpha=dist_alpha, relu_sigma=relu_sigma)
+    if white_bg:
+        cfg.flags |= L.NNR_F_WHITE_BG
+    (pts_o, pts_d, view_d), z_lo, z_hi, jit = _ray_inputs((pts_o, pts_d, view_d), z_lo, z_hi, jitter)
+    lo3, is3, d3, bits = _grid_args(grid, dev, "render_sparse")
     packed = _packed_for(cfg, list(weights), list(biases))
     out = torch.empty(R, 5, dtype=torch.float32, device=dev)
     count = cell = out4 = None
@@ -796,9 +762,6 @@ def render_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor
         count = torch.empty(R, dtype=torch.int32, device=dev)
         cell = torch.empty(R, Cn, dtype=torch.int32, device=dev)
         out4 = torch.full((R, Cn, 4), float("nan"), dtype=torch.float32, device=dev)
-    lo3 = (C.c_float * 3)(*[float(v) for v in grid.lo])
-    is3 = (C.c_float * 3)(*[float(v) for v in grid.inv_step])
-    d3 = (C.c_int32 * 3)(nx, ny, nz)
     L.check(L.load().nnr_render_sparse(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(view_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), lo3, is3, d3,
                                        L.ptr(bits), L.ptr(packed), L.ptr(out), L.ptr(count), L.ptr(cell), L.ptr(out4), L.stream()),
             "nnr_render_sparse")
@@ -912,9 +875,7 @@ def propose(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z_hi: 
     F = int(n_fine)
     dev = pts_o.device
     cfg = split2_cfg(R, Cn, hidden, dist_alpha=dist_alpha, relu_sigma=relu_sigma)
-    pts_o, pts_d = pts_o.detach().contiguous().float(), pts_d.detach().contiguous().float()
-    z_lo, z_hi = z_lo.detach().contiguous().float(), z_hi.detach().contiguous().float()
-    jit = jitter.detach().contiguous().float().view(R, Cn) if jitter is not None else None
+    (pts_o, pts_d), z_lo, z_hi, jit = _ray_inputs((pts_o, pts_d), z_lo, z_hi, jitter)
     xi = xi.detach().contiguous().float().view(R, F) if xi is not None else None
     packed = _packed_for(cfg, list(weights), list(biases))
     f32 = dict(dtype=torch.float32, device=dev)

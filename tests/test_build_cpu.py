@@ -63,10 +63,12 @@ def test_sources_lists_every_unit_once():
     b = _build()
     for src in ("nnr_march_f16.hip", "nnr_propose_f16.hip", "nnr_grid_f16.hip", "nnr_bricks_f16.hip", "nnr_depth_f16.hip", "nnr_tsdf.hip",
                 "nnr_fusion_api.cpp", "nnr_sparse_f16.hip", "nnr_sparse_api.cpp", "nnr_ray_distortion.hip", "nnr_regularise_api.cpp",
-                "nnr_wgrad_plan.cpp"):
+                "nnr_wgrad_plan.cpp", "nnr_frozen_api.cpp", "nnr_frozen_sparse.hip"):
         assert (src, ()) in b.SOURCES and os.path.exists(os.path.join(CSRC, src)), src
     assert len(set(b.SOURCES)) == len(b.SOURCES)
     assert len({b._obj_name(s, d) for s, d in b.SOURCES}) == len(b.SOURCES)
+    # the main host unit holds no device code and no other unit's text: every .cpp and .hip is an entry of SOURCES, compiled on its own
+    assert not [l for l in _lines("nnr_api.cpp") if re.match(r'#\s*include\s*["<][^">]*\.(cpp|hip)[">]', l)]
 
 
 # ------------------------------------------------------------------------------------------------------------ who depends on what
@@ -93,6 +95,12 @@ USERS = {"nnr_density_setup_f16.inc": DENSITY,
          "include/nnr_geometry.h": {"nnr_api.cpp"},
          "include/nnr_fusion.h": {"nnr_fusion_api.cpp"},
          "include/nnr_sparse.h": {"nnr_sparse_api.cpp"},
+         "nnr_grid_check.h": {"nnr_sparse_api.cpp", "nnr_frozen_api.cpp"},
+         "nnr_sparse_cell.h": {"nnr_sparse_f16.hip", "nnr_frozen_sparse.hip"},
+         "nnr_frozen_kernels.h": {"nnr_mlp_fwd_f16.hip", "nnr_mlp_dgrad_f16.hip", "nnr_frozen_sparse.hip", "nnr_frozen_api.cpp", "nnr_api.cpp"},
+         "nnr_frozen_sparse_kernels.h": {"nnr_mlp_fwd_f16.hip", "nnr_mlp_dgrad_f16.hip", "nnr_frozen_sparse.hip", "nnr_frozen_api.cpp"},
+         "include/nnr_frozen.h": {"nnr_frozen_api.cpp"},
+         "include/nnr_frozen_sparse.h": {"nnr_frozen_api.cpp"},
          "nnr_mlp_fwd_common.h": TRUNK | {"nnr_mlp_fwd.hip"},
          "nnr_split.h": SPLIT,
          "nnr_mlp_bf16.h": SPLIT | {"nnr_mlp_fwd_bf16.hip", "nnr_mlp_dgrad_bf16.hip"}}
@@ -105,7 +113,7 @@ def _header(name):
 def test_a_header_makes_exactly_the_units_that_include_it_stale():
     b = _build()
     sources = {s for s, _ in b.SOURCES}
-    assert len(sources) == 29 and len(SPLIT) == 11 and len(USERS["nnr_mlp_bf16.h"]) == 13
+    assert len(sources) == 31 and len(SPLIT) == 11 and len(USERS["nnr_mlp_bf16.h"]) == 13
     for header, want in list(USERS.items()) + [("nnr_layout.h", sources - NO_LAYOUT)]:
         assert want <= sources, header
         path = _header(header)

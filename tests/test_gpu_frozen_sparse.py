@@ -324,6 +324,50 @@ def test_operator_with_a_grid_gives_the_abis_results_and_no_weight_gradient(D, c
     assert torch.equal(plain["live"][:int(plain["n_live"])].cpu().long(), abi["live"])
 
 
+def test_dense_and_sparse_nodes_in_alternation_keep_their_entry_points_and_workspaces_apart():
+    """One operator serves both kinds: dense, sparse, dense again on one leaf set of rays, a backward behind each.  Hidden 128, 5 rays of 33
+    samples: the rays straddle the 32-sample chunks and the last workgroup is padded.  Rounds one and three are the same bits (the sparse node
+    in between left nothing behind), the sparse round is render_frozen_sparse's bit for bit, and every buffer a node handed back lies in the
+    pool of its own kind, at that kind's size."""
+    import nnr
+    from nnr import lib as L
+    from nnr import ops
+    D, R, N = 128, 5, 33
+    inp = _inputs(R, N, True, seed=21)
+    dev = inp["pts_o"].device
+    w, b = _params(D, seed=22)
+    g = torch.Generator().manual_seed(23)
+    grid = _grid64(torch.rand(64, 64, 64, generator=g) < 0.5)
+    kw = dict(hidden=D, dist_alpha=False, white_bg=False, relu_sigma=True)
+    cfg = L.make_cfg(R, N, D, dist_alpha=False, white_bg=False, relu_sigma=True, train=True)
+    lib = L.load()
+    sizes = {"frozen": lib.nnr_frozen_workspace_floats(C.byref(cfg)), "frozen_sparse": lib.nnr_frozen_sparse_workspace_floats(C.byref(cfg))}
+    assert 0 < sizes["frozen"] < sizes["frozen_sparse"]
+    for kind in sizes:
+        ops._ws_pool_of(cfg, dev, kind).clear()
+    rays = [inp[k].clone().requires_grad_(True) for k in ("pts_o", "pts_d", "view_d")]
+    rounds, pools = [], []
+    for occupancy in (None, grid, None):
+        for t in rays:
+            t.grad = None
+        rgb, dist, alpha, z = nnr.render_rays(*rays, inp["z_lo"], inp["z_hi"], inp["jitter"], w, b, frozen=True, occupancy=occupancy, **kw)
+        torch.autograd.backward([rgb, dist], [inp["d_rgb"], inp["d_dist"]])
+        torch.cuda.synchronize()
+        rounds.append(dict(rgb=rgb.detach(), dist=dist.detach(), alpha=alpha, z=z, d_pts_o=rays[0].grad, d_pts_d=rays[1].grad, d_view=rays[2].grad))
+        pools.append({kind: [(t.numel(), t.data_ptr()) for t in ops._ws_pool_of(cfg, dev, kind)] for kind in sizes})
+    for n, held in enumerate(pools):      # what lies in each pool behind round n: one buffer of the kind's own size once a node of the kind has run
+        assert [s for s, _ in held["frozen"]] == [sizes["frozen"]], (n, held)
+        assert [s for s, _ in held["frozen_sparse"]] == ([sizes["frozen_sparse"]] if n >= 1 else []), (n, held)
+    assert pools[2]["frozen"] == pools[0]["frozen"]      # round three took round one's buffer and gave it back where it was
+    _same(rounds[2], rounds[0])
+    plain = ops.render_frozen_sparse(inp["pts_o"], inp["pts_d"], inp["view_d"], inp["z_lo"], inp["z_hi"], inp["jitter"], grid, w, b,
+                                     d_rgb=inp["d_rgb"], d_dist=inp["d_dist"], debug=True, **kw)
+    torch.cuda.synchronize()
+    _same(rounds[1], plain)
+    assert 0 < int(plain["n_live"]) < R * N      # (the grid did cull: the sparse round is not the dense one under another name)
+    assert [t.numel() for t in ops._ws_pool_of(cfg, dev, "frozen_sparse")] == [sizes["frozen_sparse"]]
+
+
 def test_operator_with_a_grid_and_bf16_falls_back_and_says_so_once(counted, caplog):
     from nnr import ops
     ops._frozen_said.clear()
