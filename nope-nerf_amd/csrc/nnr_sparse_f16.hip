@@ -20,14 +20,37 @@
 //     passes; the sums are taken once behind the last pass, in the forward's order.  No atomics, every sum in a fixed order.
 // A wave past the last ray repeats the last ray and stores nothing.
 // LDS: the forward's (ring 3 panels, park 12 slots per lane, tables) + 4 x 256 bytes of lists + 4 counts.
+//
+// NNR_SPARSE_STOP=1 compiles this text a second time as sparse_stop_f16_kernel (include/nnr_sparse_stop.h: nnr_render_sparse_stop; DESIGN.md
+// section 12.1), a unit of its own: the same prologue, passes and compositing, and behind the compositing of every pass a workgroup-uniform
+// decision whether another pass is run.  A wave is DONE after pass p iff its list is exhausted (32 (p + 1) >= n_live) or its transmittance
+// carry cT < t_min (fp32 <: a NaN carry is never done by transmittance).  Lane 0 of each wave writes that flag into s_done[p & 1][wave], one
+// raw s_barrier follows (behind lgkmcnt(0) only: the first two panels of the next pass are in flight, and __syncthreads would drain them),
+// every wave reads the four flags and the loop ends where all four are set.  The flags alternate between two rows by pass parity, so that a
+// wave's write after pass p + 1 cannot land in the row a slower wave still reads for pass p.  A wave that is done by transmittance keeps
+// compositing for as long as its workgroup runs: the waves walk the weight stream together.  A workgroup that stops before its list ends has
+// the next pass's first two panels in flight (pipe.more was true during the pass): every wave waits for its own DMA pieces (vmcnt(0)) on the
+// way out of the loop, on every path, since LDS goes back with the workgroup.  + 2 x 4 flags of LDS.  Without the define nothing here changes.
 #include "nnr_trunk_f16.h"
 #include "nnr_sparse_cell.h"
 #include "nnr_sparse_kernels.h"
 
+#ifndef NNR_SPARSE_STOP
+#define NNR_SPARSE_STOP 0
+#endif
+
 namespace nnr {
 
+#if NNR_SPARSE_STOP
+#define NNR_SPARSE_KERNEL sparse_stop_f16_kernel
+typedef SparseStopArgs SparseKernelArgs;
+#else
+#define NNR_SPARSE_KERNEL sparse_f16_kernel
+typedef SparseArgs SparseKernelArgs;
+#endif
+
 template <int D>
-__global__ __launch_bounds__(256, 1) void sparse_f16_kernel(SparseArgs a) {
+__global__ __launch_bounds__(256, 1) void NNR_SPARSE_KERNEL(SparseKernelArgs a) {
     constexpr bool TRAIN = false;
     using L = Layout<D, 3>;
     using Pipe = Split2PipeT<false>;
@@ -41,6 +64,9 @@ __global__ __launch_bounds__(256, 1) void sparse_f16_kernel(SparseArgs a) {
     __shared__ __attribute__((aligned(16))) f32x4 smem[kRingF4 + kPark + (L::table_floats + 3) / 4];
     __shared__ uint8_t s_list[kWavesPerBlock][kProposeMaxC];      // per wave: the live samples' indices, increasing
     __shared__ int s_cnt[kWavesPerBlock];                         // per wave: how many
+#if NNR_SPARSE_STOP
+    __shared__ int s_done[2][kWavesPerBlock];                     // per pass parity and wave: done after that pass
+#endif
     float* const ltab = reinterpret_cast<float*>(smem + kRingF4 + kPark);
     for (int i = threadIdx.x; i < L::table_floats; i += 256) ltab[i] = a.packed[L::bias_base + i];
 
@@ -90,6 +116,9 @@ __global__ __launch_bounds__(256, 1) void sparse_f16_kernel(SparseArgs a) {
     pipe.more = n_pass > 1;
     if (n_pass > 0) pipe.start();      // (no pass: no DMA is ever in flight)
     float cT = 1.f, cr = 0.f, cg = 0.f, cb = 0.f, cz = 0.f, cw = 0.f;      // the compositing carries, across the passes
+#if NNR_SPARSE_STOP
+    int n_ran = 0;      // P_g: the passes this workgroup ran
+#endif
 #pragma unroll 1
     for (int pass = 0; pass < n_pass; ++pass) {
     int lane = lane0;      // opaque per pass (nnr_mlp_fwd_f16.hip)
@@ -188,7 +217,25 @@ __global__ __launch_bounds__(256, 1) void sparse_f16_kernel(SparseArgs a) {
     }
 #undef NNR_FINISH
     pipe.next_pass(pass + 2 < n_pass);
+#if NNR_SPARSE_STOP
+    {   // the stop: flags by pass parity, one barrier, the same four flags in every wave -> the loop ends workgroup-uniformly
+        n_ran = pass + 1;
+        const bool done = kChunk * (pass + 1) >= n_live || cT < a.t_min;      // (cT: the same value in every lane; NaN < t_min is false)
+        if (lane0 == 0) s_done[pass & 1][wave] = done ? 1 : 0;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the flag is written; the next pass's DMA stays in flight
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        int all = 1;
+#pragma unroll
+        for (int w = 0; w < kWavesPerBlock; ++w) all &= s_done[pass & 1][w];
+        if (__builtin_amdgcn_readfirstlane(all)) break;
+    }
+#endif
     }   // pass
+#if NNR_SPARSE_STOP
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // no DMA piece of this wave is in flight past here, stopped early or not
+    if (has_ray && lane0 == 0 && a.opt_passes) a.opt_passes[ray] = n_ran;
+#endif
     {
         const float sr = wave_sum(cr), sgn = wave_sum(cg), sb = wave_sum(cb), sz = wave_sum(cz), sw = wave_sum(cw);
         if (has_ray && lane0 == 0) {
@@ -201,11 +248,15 @@ __global__ __launch_bounds__(256, 1) void sparse_f16_kernel(SparseArgs a) {
     }
 }
 
+#if NNR_SPARSE_STOP
+hipError_t launch_render_sparse_stop(int D, const SparseStopArgs& a, hipStream_t st) {
+#else
 hipError_t launch_render_sparse(int D, const SparseArgs& a, hipStream_t st) {
+#endif
     if (a.R <= 0 || a.C < 1 || a.C > kProposeMaxC) return hipErrorInvalidValue;
     dim3 grid(((uint32_t)a.R + kWavesPerBlock - 1) / kWavesPerBlock), block(256);
-    if (D == 256) hipLaunchKernelGGL(sparse_f16_kernel<256>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(sparse_f16_kernel<128>, grid, block, 0, st, a);
+    if (D == 256) hipLaunchKernelGGL(NNR_SPARSE_KERNEL<256>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(NNR_SPARSE_KERNEL<128>, grid, block, 0, st, a);
     return hipGetLastError();
 }
 

@@ -27,6 +27,15 @@ struct SparseArgs {
 
 hipError_t launch_render_sparse(int D, const SparseArgs& a, hipStream_t st);      // nnr_sparse_f16.hip
 
+// the stopping render (include/nnr_sparse_stop.h): SparseArgs and what the stop needs behind it, a block of its own
+// so that sparse_f16_kernel's kernel arguments stay what they are
+struct SparseStopArgs : SparseArgs {
+    float t_min;                           // a wave is done once its transmittance carry is < t_min (fp32); 0 stops nothing
+    int32_t* opt_passes;                   // (R) or null: the passes the ray's workgroup ran
+};
+
+hipError_t launch_render_sparse_stop(int D, const SparseStopArgs& a, hipStream_t st);      // nnr_sparse_f16.hip under NNR_SPARSE_STOP=1
+
 // nnr_api.cpp: what a launcher returned -> the entry point's return code (NNR_E_HIP, the HIP error kept for nnr_last_hip_error)
 int launched(hipError_t e);
 

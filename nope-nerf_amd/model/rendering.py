@@ -238,10 +238,11 @@ class Renderer(nn.Module):
         grid = self._occupancy_grid(pixels, z_lo, kw) if cfg.get('occupancy', None) is not None else None
         if grid is not None:
             # rendering.occupancy: the sparse inference render (nnr_sparse_f16.hip), the samples in known-empty cells skipped; alpha / z_vals,
-            # if somebody reads them, still come from the dense pass below
+            # if somebody reads them, still come from the dense pass below.  rendering.occupancy.t_min (absent or 0: off; no default): early
+            # ray termination, nnr_render_sparse_stop -- a setting of the render, not of the grid: it is no part of the grid's cache key
             rgb, dist_pred, _ = _nnr_ops.render_sparse(pts_o, pts_d, view, z_lo, z_hi, jitter, grid, net.weights(), net.biases(),
                                                        hidden=kw['hidden'], dist_alpha=kw['dist_alpha'], white_bg=kw['white_bg'],
-                                                       relu_sigma=kw['relu_sigma'])
+                                                       relu_sigma=kw['relu_sigma'], t_min=float(cfg['occupancy'].get('t_min', None) or 0.0))
             alpha = z_val = None
         elif ray_distortion is not None:
             rgb, dist_pred, alpha, z_val, dloss = nnr.render_rays(pts_o, pts_d, view, z_lo, z_hi, jitter, net.weights(), net.biases(),

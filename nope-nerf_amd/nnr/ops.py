@@ -739,14 +739,22 @@ def render_depth(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z
 
 def render_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor,
                   jitter: Optional[torch.Tensor], grid, weights, biases, *, hidden: int, dist_alpha: bool, white_bg: bool, relu_sigma: bool,
-                  debug: bool = False):
+                  t_min: float = 0.0, debug: bool = False):
     """A forward-only render that evaluates the MLP only on the samples an occupancy grid does not call empty, in one launch of
     nnr_render_sparse (include/nnr_sparse.h): the inputs of a render_rays call plus `grid` -- an object with lo, inv_step (three floats each),
     dims = (n_x, n_y, n_z) cells and bits, the (n_z, n_y, ceil(n_x / 32)) int32 words on the rays' device (model.geometry.OccupancyGrid) ->
     rgb (R,3), dist (R) = sum w z, acc (R) = sum w.  A sample outside the grid, or in a cell whose bit is set, is evaluated and composited with
     the alpha it has in the dense render; a sample in a cell whose bit is clear is skipped.  Always in the two-term fp16 products
     (split2_cfg), with the cached pack, as propose.  debug: (rgb, dist, acc, count (R) int32, cell (R,C) int32, out4 (R,C,4) with NaN rows for
-    the culled samples).  Any R, 1 <= C <= 256.  Not differentiable.  No host synchronisation."""
+    the culled samples).  Any R, 1 <= C <= 256.  Not differentiable.  No host synchronisation.
+    t_min (0 <= t_min < 1; default 0: off, nnr_render_sparse exactly as without it): early ray termination, one launch of
+    nnr_render_sparse_stop (include/nnr_sparse_stop.h) -- a workgroup of four rays stops walking their live lists, 32 samples a pass, once
+    each ray's list is exhausted or its transmittance is below t_min; a ray's outputs come from the samples evaluated until then and differ
+    from the unstopped ones by at most about t_min (times the largest z for dist).  debug then also returns, as a seventh element, passes (R)
+    int32: the passes the ray's workgroup ran; out4 keeps NaN rows for the live samples that were not evaluated."""
+    t_min = float(t_min)
+    if not 0.0 <= t_min < 1.0:      # (a NaN fails)
+        raise ValueError("render_sparse: t_min must be in [0, 1); got %r" % (t_min,))
     _require_gpu(pts_o)
     R, Cn = pts_o.shape[0], z_lo.shape[0]
     dev = pts_o.device
@@ -762,6 +770,13 @@ def render_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, view_d: torch.Tensor
         count = torch.empty(R, dtype=torch.int32, device=dev)
         cell = torch.empty(R, Cn, dtype=torch.int32, device=dev)
         out4 = torch.full((R, Cn, 4), float("nan"), dtype=torch.float32, device=dev)
+    if t_min > 0.0:
+        passes = torch.empty(R, dtype=torch.int32, device=dev) if debug else None
+        L.check(L.load().nnr_render_sparse_stop(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(view_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), lo3, is3,
+                                                d3, L.ptr(bits), L.ptr(packed), t_min, L.ptr(out), L.ptr(count), L.ptr(cell), L.ptr(out4),
+                                                L.ptr(passes), L.stream()), "nnr_render_sparse_stop")
+        res = (out[:, :3], out[:, 3], out[:, 4])
+        return res + (count, cell, out4, passes) if debug else res
     L.check(L.load().nnr_render_sparse(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(view_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), lo3, is3, d3,
                                        L.ptr(bits), L.ptr(packed), L.ptr(out), L.ptr(count), L.ptr(cell), L.ptr(out4), L.stream()),
             "nnr_render_sparse")

@@ -181,11 +181,13 @@ def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_poi
     return dict(dense, frozen_occupancy=sparse)
 
 
-def occupancy_compare(cfg, nope, pose, loader, field, device, resolution, alpha_mins, dilate=1, bounds=None, frames=4):
+def occupancy_compare(cfg, nope, pose, loader, field, device, resolution, alpha_mins, dilate=1, bounds=None, frames=4, t_min=None):
     """Full frames of the first `frames` training views at their learned poses, rendered dense and with rendering.occupancy (the sparse
     inference render) for every alpha_min -> rows of {alpha_min, cells occupied, samples culled, PSNR of the sparse
     against the dense frames, seconds per frame of both}.  The culled share is counted by a debug call of nnr.ops.render_sparse on the
-    frames' rays; the timed renders run without it."""
+    frames' rays; the timed renders run without it.  t_min (rendering.occupancy.t_min: early ray termination): one more
+    row per alpha_min, the same grid rendered with the stop -- the passes its workgroups run over the passes the sparse render runs, the PSNR
+    of the stopped frames against the dense ones, seconds per frame."""
     import model as mdl
     from model import imaging
     from nnr import camera
@@ -221,7 +223,12 @@ def occupancy_compare(cfg, nope, pose, loader, field, device, resolution, alpha_
         frames_of(sparse_r)      # (builds the grid)
         sparse, t_sparse = frames_of(sparse_r)
         grid = sparse_r.__dict__["_occupancy_hit"][2]
-        live = total = 0
+        live = total = ran = parent_passes = 0
+        if t_min:
+            stop_r = mdl.Renderer(base.model, dict(cfg["rendering"], occupancy=dict(occ, t_min=float(t_min))), device=device)
+            stop_r.eval()
+            frames_of(stop_r)
+            stopped, t_stop = frames_of(stop_r)
         with torch.no_grad():
             pixels = arange_pixels(resolution=size, device=device)[1]
             depth = torch.ones(1, pixels.shape[1], 1, device=device)
@@ -234,21 +241,35 @@ def occupancy_compare(cfg, nope, pose, loader, field, device, resolution, alpha_
                 else:
                     z_lo, z_hi = sparse_r._z_tables(cfg["rendering"]["num_points"], *base.depth_range, False, device)
                 net = base.model
-                count = ops.render_sparse(origin, ray, view, z_lo, z_hi, None, grid, net.weights(), net.biases(), hidden=net.hidden_dim,
-                                          dist_alpha=bool(cfg["rendering"]["dist_alpha"]), white_bg=False,
-                                          relu_sigma=(net.occ_activation != "softplus"), debug=True)[3]
+                kw = dict(hidden=net.hidden_dim, dist_alpha=bool(cfg["rendering"]["dist_alpha"]), white_bg=False,
+                          relu_sigma=(net.occ_activation != "softplus"), debug=True)
+                count = ops.render_sparse(origin, ray, view, z_lo, z_hi, None, grid, net.weights(), net.biases(), **kw)[3]
                 live += int(count.sum())
                 total += count.numel() * int(z_lo.shape[0])
+                if t_min:      # per workgroup of four rays: the passes run with the stop, and the sparse render's own ceil(max live / 32)
+                    passes = ops.render_sparse(origin, ray, view, z_lo, z_hi, None, grid, net.weights(), net.biases(), t_min=float(t_min), **kw)[6]
+                    ran += int(passes[::4].sum())
+                    pad = torch.cat([count, count[-1:].expand((-count.numel()) % 4)]).view(-1, 4)
+                    parent_passes += int(((pad.max(1)[0] + 31) // 32).sum())
         mse = float(torch.nn.functional.mse_loss(sparse, dense))
         rows.append({"alpha_min": float(alpha_min), "resolution": int(resolution), "cells_occupied": float(grid.occupied),
                      "samples_culled": 1. - live / max(total, 1), "psnr_sparse_vs_dense": float(mse2psnr(mse)) if mse > 0. else float("inf"),
                      "seconds_per_frame_dense": t_dense, "seconds_per_frame_sparse": t_sparse, "frames": len(mats)})
         print(json.dumps({"occupancy": rows[-1]}), flush=True)
+        if t_min:
+            mse_s, mse_p = float(torch.nn.functional.mse_loss(stopped, dense)), float(torch.nn.functional.mse_loss(stopped, sparse))
+            rows.append({"alpha_min": float(alpha_min), "resolution": int(resolution), "t_min": float(t_min),
+                         "passes_run": ran, "passes_of_sparse": parent_passes, "passes_over_sparse": ran / max(parent_passes, 1),
+                         "psnr_stop_vs_dense": float(mse2psnr(mse_s)) if mse_s > 0. else float("inf"),
+                         "psnr_stop_vs_sparse": float(mse2psnr(mse_p)) if mse_p > 0. else float("inf"),
+                         "seconds_per_frame_dense": t_dense, "seconds_per_frame_sparse": t_sparse, "seconds_per_frame_stop": t_stop,
+                         "frames": len(mats)})
+            print(json.dumps({"occupancy_stop": rows[-1]}), flush=True)
     return rows
 
 
 def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=None, eval_epochs=0, eval_dir=None, checkpoint_dir=None,
-        occupancy=None, frozen_eval=True, frozen_occupancy=None, **cfg_kw):
+        occupancy=None, frozen_eval=True, frozen_occupancy=None, t_min=None, **cfg_kw):
     """-> dict with the per-epoch PSNR / pose-error curve and the loop throughput (+ novel-view scores with eval_epochs > 0)."""
     import dataloading as dl
     from model.common import mse2psnr
@@ -305,7 +326,7 @@ def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=No
         if num_fine_of(cfg):
             raise ValueError("--occupancy compares plain renders: leave --num-fine off")
         occ_rows = occupancy_compare(cfg, trainer.model, pose, loader, field, device, occupancy[0], occupancy[1],
-                                     bounds=[[-1.5, -1.5, -1.], [1.5, 1.5, 1.]] if style == "llff" else None)
+                                     bounds=[[-1.5, -1.5, -1.], [1.5, 1.5, 1.]] if style == "llff" else None, t_min=t_min)
     return {"novel_views": novel, "occupancy": occ_rows, "scene": scene, "style": style, "views": n_views, "image": [field.H, field.W], "rays_per_step": n_rays,
             "samples_per_ray": cfg["rendering"]["num_points"], "fine_samples_per_ray": cfg["rendering"].get("num_fine", 0), "proposal": cfg["rendering"].get("proposal", "render"), "hidden": cfg["model"]["hidden_dim"], "epochs": epochs,
             "steps": it + 1, "loader": "resident" if cfg["dataloading"]["resident"] else "host(workers=%d)" % cfg["dataloading"]["n_workers"],
@@ -334,6 +355,9 @@ def main():
     ap.add_argument("--occupancy", nargs="+", default=None, metavar=("RES", "ALPHA_MIN"),
                     help="after training: render evaluation frames dense and with rendering.occupancy {resolution: RES, alpha_min: ALPHA_MIN} "
                          "(several ALPHA_MIN: one row each); prints the culled share and the PSNR of the sparse against the dense frames")
+    ap.add_argument("--t-min", type=float, default=None, metavar="T",
+                    help="with --occupancy: also render with rendering.occupancy.t_min: T (early ray termination); one more row per ALPHA_MIN "
+                         "with the passes run over the sparse render's and the PSNR of the stopped against the dense frames")
     ap.add_argument("--ray-distortion", type=float, default=0.0, metavar="W",
                     help="training.ray_distortion_weight: the weight of the ray distortion of the compositing weights (0 = off; e.g. 0.01)")
     ap.add_argument("--log-every", type=int, default=10)
@@ -350,10 +374,12 @@ def main():
     if a.occupancy is not None and len(a.occupancy) < 2:
         ap.error("--occupancy RES ALPHA_MIN [ALPHA_MIN ...]")
     occupancy = None if a.occupancy is None else (int(a.occupancy[0]), [float(v) for v in a.occupancy[1:]])
+    if a.t_min is not None and (occupancy is None or not 0. < a.t_min < 1.):
+        ap.error("--t-min T goes with --occupancy and lies in (0, 1)")
     res = run(a.path, a.scene, style=a.style, epochs=a.epochs, log_every=a.log_every, eval_epochs=a.eval_epochs, eval_dir=a.eval_dir, checkpoint_dir=a.checkpoint_dir, n_rays=a.rays, n_samples=a.samples,
               hidden=a.hidden, resident=not a.host_loader, aux=not a.no_aux, resize_factor=a.factor, workers=a.workers,
               mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine, proposal=a.proposal, occupancy=occupancy,
-              ray_distortion=a.ray_distortion, frozen_eval=not a.no_frozen_eval,
+              ray_distortion=a.ray_distortion, frozen_eval=not a.no_frozen_eval, t_min=a.t_min,
               frozen_occupancy=None if a.frozen_occupancy is None else (int(a.frozen_occupancy[0]), float(a.frozen_occupancy[1])))
     print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
     if a.out:
