@@ -16,26 +16,122 @@
 // A sample is NaN (alpha, and with it the ray's whole row) where an activation left fp16's range (left_f16_range), where its point is not
 // finite (ReLU would turn the NaN products into zeros, as it does behind an overflow) or where the raw density is NaN (fmaxf(raw, 0) of
 // NNR_F_RELU_SIGMA would drop it).  No atomics, every sum in a fixed order: bit-reproducible.
+//
+// NNR_PROPOSE_SPARSE=1 compiles this text a second time as propose_sparse_f16_kernel (include/nnr_propose_sparse.h: nnr_propose_sparse;
+// DESIGN.md section 12.2), a unit of its own: the same passes and the same row code behind the compaction prologue of sparse_f16_kernel
+// (nnr_sparse_f16.hip).  Without the define nothing here changes.
+//   * prologue, in front of the setup (whose workgroup barrier, the one in front of the weight stream, then covers the tables AND the four
+//     lists: there is no second one): lane l takes the samples j = l + 64 k, makes z_j and p_j with the expressions of the passes, looks the
+//     cell up (sparse_cell, nnr_cell_rule.h: fp32, a NaN is outside) and reads the cell's bit with a plain vector load.  A sample is live
+//     iff it is outside the grid or its bit is set.  Ballot and popcount compact the live j in increasing order into the wave's LDS list,
+//     the count beside it.  The lane keeps z_j (staged for EVERY j < C once the setup has carved LDS up: the neighbours' deltas, the CDF
+//     edges and the merged row need a culled sample's depth too) and a bit per round: whether its sample is live.
+//   * n_pass = the largest ceil(n_live / 32) of the four waves, workgroup-uniform, before pipe.start().  A workgroup without a live sample
+//     starts no DMA and runs no pass.
+//   * passes: lane `col` takes j = list[32 pass + col]; a slot past n_live takes a clamped index, is computed like any other and is not
+//     staged.
+//   * behind the last pass a live sample's alpha is the dense kernel's (the delta to the next sample of the ORIGINAL row, the NaN rules
+//     above); a culled sample's is 0.0f BY SELECT on the lane's liveness bit, whatever the flags (also the closing sample of
+//     NNR_F_DIST_ALPHA): its staged density is never read, liveness is never encoded in a density.  resample_row runs on the full row.
+// A culled sample is not evaluated and so cannot make its ray NaN: the one intended difference from the dense kernel.
+// LDS: the dense kernel's + 4 x 256 bytes of lists + 4 counts.
 #include "nnr_trunk_f16.h"
 #include "nnr_resample_row.h"
+#include "nnr_cell_rule.h"
+#include "nnr_propose_sparse_kernels.h"
+
+#ifndef NNR_PROPOSE_SPARSE
+#define NNR_PROPOSE_SPARSE 0
+#endif
 
 namespace nnr {
 
+#if NNR_PROPOSE_SPARSE
+#define NNR_PROPOSE_KERNEL propose_sparse_f16_kernel
+typedef ProposeSparseArgs ProposeKernelArgs;
+#else
+#define NNR_PROPOSE_KERNEL propose_f16_kernel
+typedef ProposeArgs ProposeKernelArgs;
+#endif
+
 template <int D>
-__global__ __launch_bounds__(256, 1) void propose_f16_kernel(ProposeArgs a) {
+__global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a) {
     constexpr int kDensityExtraF4 = kWavesPerBlock * 2 * kProposeMaxC / 4;      // per wave the raw densities and the depths of its ray
+#if NNR_PROPOSE_SPARSE
+    // ---- prologue: which samples are live (sparse_f16_kernel's, with the depths kept) ----
+    constexpr int kRounds = kProposeMaxC / 64;
+    __shared__ uint8_t s_list[kWavesPerBlock][kProposeMaxC];      // per wave: the live samples' indices, increasing
+    __shared__ int s_cnt[kWavesPerBlock];                         // per wave: how many
+    int n_live = 0;
+    uint32_t live_bits = 0;      // bit k: this lane's sample lane + 64 k is live
+    float zk[kRounds];           // the depth of this lane's sample lane + 64 k
+    {
+        const int pl = threadIdx.x & 63, pw = threadIdx.x >> 6;
+        const int p_ray_u = blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane(pw);
+        const bool p_has = p_ray_u < a.R;
+        const int p_ray = p_has ? p_ray_u : a.R - 1;
+        const float* const ro = a.pts_o + 3 * (int64_t)p_ray;
+        const float* const rd = a.pts_d + 3 * (int64_t)p_ray;
+        const int64_t row0 = (int64_t)p_ray * a.C;
+#pragma unroll
+        for (int k = 0; k < kRounds; ++k) {
+            zk[k] = 0.f;
+            if (64 * k < a.C) {
+                const int j = pl + 64 * k;
+                const bool valid = j < a.C;
+                const int jc = valid ? j : a.C - 1;
+                const float zlo = a.z_lo[jc], zhi = a.z_hi[jc];
+                float z = zlo;
+                if (a.jitter) z = __fadd_rn(zlo, __fmul_rn(__fsub_rn(zhi, zlo), a.jitter[row0 + jc]));
+                const float px = __fadd_rn(ro[0], __fmul_rn(rd[0], z));
+                const float py = __fadd_rn(ro[1], __fmul_rn(rd[1], z));
+                const float pz = __fadd_rn(ro[2], __fmul_rn(rd[2], z));
+                int word, bit;
+                const int cell = sparse_cell(a, px, py, pz, word, bit);
+                bool lv = valid;
+                if (cell >= 0) lv = valid && ((a.bits[word] >> bit) & 1u) != 0;
+                const uint64_t m = __ballot(lv);
+                const int pos = n_live + __popcll(m & ((1ull << pl) - 1ull));
+                if (lv) s_list[pw][pos] = (uint8_t)j;
+                if (valid && p_has && a.opt_cell) a.opt_cell[row0 + j] = cell;
+                n_live += __popcll(m);
+                live_bits |= lv ? 1u << k : 0u;
+                zk[k] = z;
+            }
+        }
+        n_live = __builtin_amdgcn_readfirstlane(n_live);
+        if (pl == 0) {
+            s_cnt[pw] = n_live;
+            if (p_has && a.opt_count) a.opt_count[p_ray] = n_live;
+        }
+    }
+#endif
 #include "nnr_density_setup_f16.inc"
     static_assert(kWavesPerBlock * (2 * kProposeMaxC + 2 * kResampleMaxN) <= kRingF4 * 4, "the rows of the resampling stage fit in the weight ring");
     const int C = a.C, F = a.F;
+#if NNR_PROPOSE_SPARSE
+    int n_pass = 0;      // (behind the setup's barrier: the four counts are visible)
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; ++w) n_pass = max(n_pass, (s_cnt[w] + kChunk - 1) / kChunk);
+    n_pass = __builtin_amdgcn_readfirstlane(n_pass);
+    pipe.more = n_pass > 1;
+    if (n_pass > 0) pipe.start();      // (no pass: no DMA is ever in flight)
+#else
     const int n_pass = (C + kChunk - 1) / kChunk;
     pipe.more = n_pass > 1;
     pipe.start();
+#endif
 
     const int wave_ray = blockIdx.x * kWavesPerBlock + wave_u;
     const bool live = wave_ray < a.R;
     const int ray = live ? wave_ray : a.R - 1;
     float* const s_raw = reinterpret_cast<float*>(smem + kRingF4 + kPark) + wave * (2 * kProposeMaxC);
     float* const s_z = s_raw + kProposeMaxC;
+#if NNR_PROPOSE_SPARSE
+#pragma unroll
+    for (int k = 0; k < kRounds; ++k)      // every depth of the row, culled or not (read behind the barrier that follows the passes)
+        if (lane0 + 64 * k < C) s_z[lane0 + 64 * k] = zk[k];
+#endif
 
 #pragma unroll 1
     for (int pass = 0; pass < n_pass; ++pass) {
@@ -47,8 +143,17 @@ __global__ __launch_bounds__(256, 1) void propose_f16_kernel(ProposeArgs a) {
     f32x4* const park = smem + kRingF4 + wave * (8 * 64) + lane;
 
     // ---- sampling, as the forward kernel's: unfused mul/add ----
+#if NNR_PROPOSE_SPARSE
+    const int slot = pass * kChunk + col;
+    const bool dead = slot >= n_live;      // a slot past the list: computed on a clamped index, not staged
+    int jl = 0;
+    if (n_live > 0) jl = s_list[wave][dead ? n_live - 1 : slot];
+    const int j = jl < C ? jl : C - 1;
+    const int jc = j;
+#else
     const int j = pass * kChunk + col;
     const int jc = j < C ? j : C - 1;
+#endif
     const float zlo = a.z_lo[jc], zhi = a.z_hi[jc];
     float z = zlo;
     if (a.jitter) z = __fadd_rn(zlo, __fmul_rn(__fsub_rn(zhi, zlo), a.jitter[(int64_t)ray * C + jc]));
@@ -61,10 +166,14 @@ __global__ __launch_bounds__(256, 1) void propose_f16_kernel(ProposeArgs a) {
 #include "nnr_density_pass_f16.inc"
     const bool finite_p = fabsf(px) < __uint_as_float(0x7f800000u) && fabsf(py) < __uint_as_float(0x7f800000u) && fabsf(pz) < __uint_as_float(0x7f800000u);
     if (left_f16_range(mx) || !finite_p) raw = __uint_as_float(0x7fc00000u);
+#if NNR_PROPOSE_SPARSE
+    if (half == 0 && !dead) s_raw[j] = raw;      // (its depth is staged already)
+#else
     if (half == 0 && j < C) {
         s_raw[j] = raw;
         s_z[j] = z;
     }
+#endif
     pipe.next_pass(pass + 2 < n_pass);
     }   // pass
 
@@ -76,11 +185,22 @@ __global__ __launch_bounds__(256, 1) void propose_f16_kernel(ProposeArgs a) {
     float* const fs = cdf + Cp;
     float* const out = fs + Fp;
     bool bad = false;
+#if NNR_PROPOSE_SPARSE
+    if (live && lane0 == 0 && a.opt_passes) a.opt_passes[ray] = n_pass;
+#endif
     for (int i = lane0; i < C; i += 64) {
+#if NNR_PROPOSE_SPARSE
+        const bool lv = ((live_bits >> (i >> 6)) & 1u) != 0;      // sample i = lane0 + 64 k is this lane's sample of round k
+        const float raw = lv ? s_raw[i] : 0.f, zz = s_z[i];       // (a culled sample's density was never staged)
+#else
         const float raw = s_raw[i], zz = s_z[i];
+#endif
         float unused;
         float al = sample_alpha(raw, i + 1 < C ? s_z[i + 1] - zz : 1e10f, i == C - 1, a.flags, unused);
         if (raw != raw) al = __uint_as_float(0x7fc00000u);
+#if NNR_PROPOSE_SPARSE
+        al = lv ? al : 0.0f;      // by select: whatever the flags made of a density of 0
+#endif
         bad = bad || (al != al) || (zz != zz);
         out[i] = al;
         if (live) {
@@ -94,11 +214,15 @@ __global__ __launch_bounds__(256, 1) void propose_f16_kernel(ProposeArgs a) {
                  a.opt_fine ? a.opt_fine + (int64_t)ray * F : nullptr, lane0, live, bad);
 }
 
+#if NNR_PROPOSE_SPARSE
+hipError_t launch_propose_sparse(int D, const ProposeSparseArgs& a, hipStream_t st) {
+#else
 hipError_t launch_propose(int D, const ProposeArgs& a, hipStream_t st) {
+#endif
     if (a.R <= 0 || a.C < 3 || a.C > kProposeMaxC || a.F < 1 || a.C + a.F > kResampleMaxN) return hipErrorInvalidValue;
     dim3 grid((a.R + kWavesPerBlock - 1) / kWavesPerBlock), block(256);
-    if (D == 256) hipLaunchKernelGGL(propose_f16_kernel<256>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(propose_f16_kernel<128>, grid, block, 0, st, a);
+    if (D == 256) hipLaunchKernelGGL(NNR_PROPOSE_KERNEL<256>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(NNR_PROPOSE_KERNEL<128>, grid, block, 0, st, a);
     return hipGetLastError();
 }
 

@@ -9,7 +9,8 @@ eval_pose.occupancy (absent = false: nothing changes; needs frozen_field): the F
 rendering.occupancy settings (Renderer.frozen_occupancy_grid: geometry.occupancy_grid at level_for_alpha, the same bounds rules), keeps it
 for the trainer's lifetime and runs every step under nnr.frozen_field(occupancy=grid): the samples in cells the grid calls empty are skipped,
 forward and backward.  The grid is valid because the field is frozen by this trainer's own declaration; the pose
-optimiser's steps do not touch it.  Where the renderer refuses a grid (CPU tensors, bf16 products, too many samples) the dense frozen path
+optimiser's steps do not touch it.  With rendering.occupancy.proposal: true (and rendering.num_fine, rendering.proposal 'density') the
+proposal of every step skips the coarse samples that grid calls empty as well.  Where the renderer refuses a grid (CPU tensors, bf16 products, too many samples) the dense frozen path
 runs."""
 import contextlib
 import logging

@@ -12,6 +12,8 @@ network: a coarse forward-only pass at the `num_points - outside_steps` samples 
 depths per ray from the coarse weights' inverse CDF, and the render proper -- the training path -- at the sorted union of both sets.
 `rendering.proposal: 'density'` (default 'render'; no reference counterpart either) replaces the coarse pass and the resampling launch by
 one launch of the fused proposal kernel (`nnr.ops.propose`, nnr_propose_f16.hip): the density of the coarse samples alone.
+`rendering.occupancy.proposal: true` (default false) makes that launch skip the coarse samples the render's occupancy grid calls empty
+(`nnr.ops.propose_sparse`), wherever such a grid applies -- the sparse inference render's, or the one of `nnr.frozen_field(occupancy=grid)`.
 
 `rendering.normal_loss: True` (reference :133-143; off by default, and no loss term of the reference consumes it) adds the
 normal-consistency vector `out['normal']`: second-order autograd through the MLP trunk for the 2 M surface points, in stock torch
@@ -200,10 +202,17 @@ class Renderer(nn.Module):
                   relu_sigma=(net.occ_activation != 'softplus'),
                   bf16=(str(cfg.get('mfma_dtype', 'fp32')).lower() == 'bf16'))   # rendering.mfma_dtype: fp32 (default) | bf16
         n_fine = int(cfg.get('num_fine', 0) or 0)    # rendering.num_fine: hierarchical sampling, 0 / absent = off (nothing below changes)
+        grid, grid_asked = None, False      # rendering.occupancy: the render's grid, and whether it has been asked for already
         if n_fine > 0:
             proposal = cfg.get('proposal', None) or 'render'      # rendering.proposal (absent = 'render'; ignored without num_fine)
             if proposal not in ('render', 'density'):
                 raise ValueError("rendering.proposal: expected 'render' or 'density', got %r" % (proposal,))
+            # rendering.occupancy.proposal (absent = false; ignored without num_fine, as rendering.proposal is): the proposal skips the coarse
+            # samples the grid calls empty.  A setting of the render, not of the grid: it is no part of the grid's cache key
+            sparse_proposal = bool((cfg.get('occupancy', None) or {}).get('proposal', False))
+            if sparse_proposal and proposal != 'density':
+                raise ValueError("rendering.occupancy.proposal: true needs rendering.proposal: 'density' (there is no sparse %r proposal)"
+                                 % (proposal,))
             if not pixels.is_cuda:
                 raise NotImplementedError("rendering.num_fine > 0 runs only on the GPU (HIP resampling kernel, nnr_resample.hip); there is no "
                                           "CPU hierarchical sampling -- set rendering.num_fine: 0 for CPU runs")
@@ -214,8 +223,20 @@ class Renderer(nn.Module):
             # (nnr_propose_f16.hip through nnr.ops.propose): the coarse samples' density alone, always in the two-term fp16 products.
             xi = self._fine_draw(n_rays, n_fine, device) if (jitter is not None) else None   # after the jitter draw; else u at bin centres
             if proposal == 'density':
-                z_all = _nnr_ops.propose(pts_o, pts_d, z_lo, z_hi, jitter, xi, n_fine, net.weights(), net.biases(), hidden=kw['hidden'],
-                                         dist_alpha=kw['dist_alpha'], relu_sigma=kw['relu_sigma'])
+                pgrid = None
+                if sparse_proposal:
+                    # the grid the render below uses, asked for in front of the proposal (its sample count is known: the union's); inside
+                    # nnr.frozen_field(occupancy=grid) -- pose refinement, gradients enabled -- that block's grid, the one render_rays uses
+                    # there.  Where the grid is refused (one logged line) the dense proposal runs
+                    grid, grid_asked = self._occupancy_grid(pixels, n_samples + n_fine, kw), True
+                    pgrid = grid
+                    if pgrid is None and not kw['bf16']:
+                        pgrid = _nnr_ops.frozen_occupancy()
+                pkw = dict(hidden=kw['hidden'], dist_alpha=kw['dist_alpha'], relu_sigma=kw['relu_sigma'])
+                if pgrid is not None:      # nnr_propose_f16.hip under NNR_PROPOSE_SPARSE=1, through nnr.ops.propose_sparse
+                    z_all = _nnr_ops.propose_sparse(pts_o, pts_d, z_lo, z_hi, jitter, xi, n_fine, pgrid, net.weights(), net.biases(), **pkw)
+                else:
+                    z_all = _nnr_ops.propose(pts_o, pts_d, z_lo, z_hi, jitter, xi, n_fine, net.weights(), net.biases(), **pkw)
                 z_lo, z_hi = self._unit_tables(n_samples + n_fine, device)
                 jitter = z_all
             else:      # today's path, as it was written
@@ -235,7 +256,8 @@ class Renderer(nn.Module):
             else:
                 ray_distortion = (float(self.depth_range[0]), 1.0 / (float(self.depth_range[1]) - float(self.depth_range[0])))
         lazy_samples = not torch.is_grad_enabled()   # evaluation / visualisation: per-sample outputs only if somebody reads them
-        grid = self._occupancy_grid(pixels, z_lo, kw) if cfg.get('occupancy', None) is not None else None
+        if not grid_asked and cfg.get('occupancy', None) is not None:
+            grid = self._occupancy_grid(pixels, int(z_lo.shape[0]), kw)
         if grid is not None:
             # rendering.occupancy: the sparse inference render (nnr_sparse_f16.hip), the samples in known-empty cells skipped; alpha / z_vals,
             # if somebody reads them, still come from the dense pass below.  rendering.occupancy.t_min (absent or 0: off; no default): early
@@ -287,9 +309,9 @@ class Renderer(nn.Module):
                   bf16=(str(cfg.get('mfma_dtype', 'fp32')).lower() == 'bf16'))
         n_render = int(cfg['num_points']) + int(cfg.get('num_fine', 0) or 0)
         with torch.no_grad():
-            return self._occupancy_grid(torch.empty(0, device=device), torch.empty(n_render), kw, frozen=True)
+            return self._occupancy_grid(torch.empty(0, device=device), n_render, kw, frozen=True)
 
-    def _occupancy_grid(self, pixels, z_lo, kw, frozen=False):
+    def _occupancy_grid(self, pixels, n_render, kw, frozen=False):
         """rendering.occupancy: {resolution: N, alpha_min: A, dilate: 1, bounds: [lo, hi]} -> the occupancy grid of the sparse inference render
         (model.geometry.occupancy_grid), or None where the dense path has to run (one logged line per reason).  N cells per axis over
         `bounds` (two scalars or two triples; default: the cube of rendering.radius under sample_option 'uniform'; required under 'ndc', where
@@ -300,8 +322,7 @@ class Renderer(nn.Module):
         from . import geometry
         cfg = self.cfg
         occ = cfg['occupancy']
-        n_render = int(z_lo.shape[0])
-        why = None
+        why = None      # (n_render: the samples per ray of the render the grid is for)
         if torch.is_grad_enabled() and not frozen:
             why = "gradients are enabled (the sparse render is forward-only)"
         elif not pixels.is_cuda:

@@ -490,6 +490,13 @@ def frozen_field(occupancy=None):
         _frozen_state.on, _frozen_state.grid = prev
 
 
+def frozen_occupancy():
+    """The occupancy grid of the enclosing nnr.frozen_field(occupancy=grid) on this thread, or None (outside such a block, or inside one
+    that was given no grid): what a render_rays call with frozen=None would use.  For callers that run other kernels on the same frozen
+    field, such as the renderer's sparse proposal (model/rendering.py)."""
+    return getattr(_frozen_state, "grid", None) if getattr(_frozen_state, "on", False) else None
+
+
 def _frozen_fallback_reason(pts_o, pts_d, view_d, bf16):
     """Why the frozen kernels do not apply to this call (None: they do).  They exist for the two-term fp16 products alone, and only a call
     that differentiates a ray input has a use for them."""
@@ -900,3 +907,44 @@ def propose(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z_hi: 
     L.check(L.load().nnr_propose(C.byref(cfg), F, L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), L.ptr(xi), L.ptr(packed),
                                  L.ptr(z_all), L.ptr(alpha_c), L.ptr(z_c), L.ptr(fine), L.stream()), "nnr_propose")
     return (z_all, alpha_c, z_c, fine) if debug else z_all
+
+
+propose_sparse_tally = None      # tools: while this is a list, every propose_sparse call appends (live coarse samples (1) tensor, R C)
+
+
+def propose_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor, jitter: Optional[torch.Tensor],
+                   xi: Optional[torch.Tensor], n_fine: int, grid, weights, biases, *, hidden: int, dist_alpha: bool, relu_sigma: bool,
+                   debug: bool = False):
+    """propose that does not evaluate the coarse samples an occupancy grid calls empty, in one launch of nnr_propose_sparse
+    (include/nnr_propose_sparse.h; rendering.occupancy.proposal): propose's inputs plus `grid`, as render_sparse takes it -> z_all
+    (R, C + n_fine), bit for bit what resample(alpha', z, xi, n_fine) gives, alpha' being propose's alpha where the sample is live (outside
+    the grid, or in a cell whose bit is set) and 0 where it is culled.  With every bit set that is propose's output bit for bit; a ray
+    without a live sample gets the row resample makes from zeros.  A culled sample is not evaluated and so cannot make its ray NaN.  The
+    cached pack, as propose.  debug: (z_all, alpha_c (R,C) = alpha', z_c (R,C), fine (R,n_fine), count (R) int32, cell (R,C) int32,
+    passes (R) int32: the passes of 32 samples the ray's workgroup of four rays ran).  Not differentiable.  3 <= C <= 256,
+    C + n_fine <= 1024.  No host synchronisation."""
+    _require_gpu(pts_o)
+    R, Cn = pts_o.shape[0], z_lo.shape[0]
+    F = int(n_fine)
+    dev = pts_o.device
+    cfg = split2_cfg(R, Cn, hidden, dist_alpha=dist_alpha, relu_sigma=relu_sigma)
+    (pts_o, pts_d), z_lo, z_hi, jit = _ray_inputs((pts_o, pts_d), z_lo, z_hi, jitter)
+    xi = xi.detach().contiguous().float().view(R, F) if xi is not None else None
+    lo3, is3, d3, bits = _grid_args(grid, dev, "propose_sparse")
+    packed = _packed_for(cfg, list(weights), list(biases))
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    z_all = torch.empty(R, Cn + max(F, 0), **f32)
+    alpha_c = z_c = fine = count = cell = passes = None
+    tally = propose_sparse_tally
+    if debug:
+        alpha_c, z_c, fine = torch.empty(R, Cn, **f32), torch.empty(R, Cn, **f32), torch.empty(R, max(F, 0), **f32)
+        count, cell, passes = torch.empty(R, **i32), torch.empty(R, Cn, **i32), torch.empty(R, **i32)
+    elif tally is not None:
+        count = torch.empty(R, **i32)
+    L.check(L.load().nnr_propose_sparse(C.byref(cfg), F, L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), L.ptr(xi), lo3, is3, d3,
+                                        L.ptr(bits), L.ptr(packed), L.ptr(z_all), L.ptr(alpha_c), L.ptr(z_c), L.ptr(fine), L.ptr(count),
+                                        L.ptr(cell), L.ptr(passes), L.stream()), "nnr_propose_sparse")
+    if tally is not None:
+        tally.append((count.sum(), R * Cn))
+    return (z_all, alpha_c, z_c, fine, count, cell, passes) if debug else z_all

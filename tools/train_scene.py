@@ -12,6 +12,12 @@ one.  GPU only (the render path has no CPU fallback).
 print, per ALPHA_MIN, the share of samples culled and the PSNR of the sparse against the dense frames (style tanks: the grid covers the cube
 of rendering.radius).
 
+--sparse-proposal (with --occupancy or --frozen-occupancy, together with --num-fine F --proposal density): rendering.occupancy.proposal:
+true, the proposal of hierarchical sampling skips the coarse samples the grid calls empty.  With --occupancy the
+frames are the sparse hierarchical render's, once with the dense and once with the sparse proposal: per ALPHA_MIN the share of coarse samples
+culled and the PSNR of the sparse-proposal frames against the dense-proposal frames.  With --frozen-occupancy the second pose refinement
+proposes through its grid and reports the share of coarse samples culled.
+
 --ray-distortion W: training.ray_distortion_weight = W, the weight of the ray distortion of the compositing weights (DESIGN.md section 13;
 0 = off, the default; the paper's example is 0.01).  The last logged line then carries the epoch's mean loss_ray_distortion.
 
@@ -108,7 +114,8 @@ def pose_errors(pose_net, gt_poses, n_views):
     return {"ate": float(compute_ATE(gt, aligned)), "rpe_trans_x100": float(rpe_t * 100), "rpe_rot_deg": float(np.degrees(rpe_r))}
 
 
-def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_points=1024, frozen_field=True, frozen_occupancy=None):
+def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_points=1024, frozen_field=True, frozen_occupancy=None,
+                    sparse_proposal=False):
     """What reference evaluation/eval.py:54-186 does for the held-out views: initialise their poses from the learned training
     trajectory (init_method 'pre': the training pose just before each held-out frame), optimise them against the frozen field
     (Trainer_pose, Adam 1e-3 halved five times), then render every held-out frame in full and score it.  LPIPS needs a VGG
@@ -116,7 +123,9 @@ def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_poi
     operator's frozen-field mode -- same losses and poses, no weight gradient; the path taken is printed.
     frozen_occupancy = (resolution, alpha_min) (--frozen-occupancy; eval_pose.occupancy: true): the same refinement is run a second time from
     the same initial poses with an occupancy grid of the field, built once, the samples it calls empty skipped forward and backward
-    (DESIGN.md section 15); the result carries the culled share, the largest distance between the two runs' refined poses and both PSNRs."""
+    (DESIGN.md section 15); the result carries the culled share, the largest distance between the two runs' refined poses and both PSNRs.
+    sparse_proposal (--sparse-proposal; rendering.occupancy.proposal: true): that second refinement also proposes through the grid
+    (DESIGN.md section 12.2); the result then carries the share of coarse samples its proposals culled."""
     import dataloading as dl
     import model as mdl
     from model.eval_images import Eval_Images
@@ -142,9 +151,11 @@ def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_poi
         first = last = None
         from nnr import ops
         ops.frozen_sparse_tally = [] if occupancy else None
+        ops.propose_sparse_tally = [] if occupancy and sparse_proposal else None
         try:
             if occupancy:      # (the key is the renderer's; it is taken away again before the frames are rendered: those stay dense)
-                nope.renderer.cfg["occupancy"] = {"resolution": int(frozen_occupancy[0]), "alpha_min": float(frozen_occupancy[1])}
+                nope.renderer.cfg["occupancy"] = {"resolution": int(frozen_occupancy[0]), "alpha_min": float(frozen_occupancy[1]),
+                                                  **({"proposal": True} if sparse_proposal else {})}
             for e in range(epochs):
                 l2 = torch.stack([tp.train_step(batch)["loss"].detach() for batch in loader]).mean()
                 sched.step()
@@ -153,6 +164,7 @@ def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_poi
                     first, last = (v, last) if e == 0 else (first, v)
         finally:
             tally, ops.frozen_sparse_tally = ops.frozen_sparse_tally, None
+            ptally, ops.propose_sparse_tally = ops.propose_sparse_tally, None
             if occupancy:
                 nope.renderer.cfg.pop("occupancy", None)
         eval_pose.eval()
@@ -170,6 +182,9 @@ def novel_view_eval(cfg, nope, pose, train_field, device, epochs, out_dir, n_poi
             live, total = float(torch.stack([t[0] for t in tally]).sum()), float(sum(t[1] for t in tally))
             res.update(samples_culled=1. - live / total, grid_builds=tp.occupancy_builds,
                        cells_occupied=float(tp.occupancy_grid.occupied) if tp.occupancy_grid is not None else None)
+        if ptally:
+            live, total = float(torch.stack([t[0] for t in ptally]).sum()), float(sum(t[1] for t in ptally))
+            res.update(coarse_samples_culled=1. - live / total)
         return res, c2ws
 
     dense, c2ws = refine_and_score(False)
@@ -268,8 +283,60 @@ def occupancy_compare(cfg, nope, pose, loader, field, device, resolution, alpha_
     return rows
 
 
+def sparse_proposal_compare(cfg, nope, pose, loader, field, device, resolution, alpha_mins, dilate=1, bounds=None, frames=4):
+    """--sparse-proposal with --occupancy: full frames of the first `frames` training views at their learned poses through the sparse
+    hierarchical render (rendering.occupancy with rendering.num_fine and rendering.proposal 'density'), once with the dense proposal
+    (rendering.occupancy.proposal absent) and once with the sparse one (true), for every alpha_min -> rows of
+    {alpha_min, cells occupied, the share of coarse samples the proposal culled, PSNR of the sparse-proposal frames against the
+    dense-proposal frames, seconds per frame of both}.  The culled share is tallied by nnr.ops.propose_sparse itself (propose_sparse_tally)."""
+    import model as mdl
+    from model import imaging
+    from model.common import mse2psnr
+    from nnr import ops
+    base = nope.renderer
+    views = []
+    for batch in loader:
+        if len(views) >= frames:
+            break
+        views.append((batch["img.camera_mat"].to(device), batch["img.scale_mat"].to(device), int(batch["img.idx"])))
+    with torch.no_grad():
+        mats = [(cam, imaging.inverse_pose(pose(i)), scale) for cam, scale, i in views]
+    size = (field.H, field.W)
+
+    def frames_of(renderer):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = [imaging.render_full_image(renderer, size, cam, world, scale, "nope_nerf", device)[0] for cam, world, scale in mats]
+        torch.cuda.synchronize()
+        return torch.stack(out), (time.perf_counter() - t0) / len(mats)
+
+    rows = []
+    for alpha_min in alpha_mins:
+        occ = {"resolution": int(resolution), "alpha_min": float(alpha_min), "dilate": int(dilate)}
+        if bounds is not None:
+            occ["bounds"] = list(bounds)
+        res = {}
+        for key in (False, True):
+            r = mdl.Renderer(base.model, dict(cfg["rendering"], occupancy=dict(occ, proposal=True) if key else dict(occ)), device=device)
+            r.eval()
+            frames_of(r)      # (builds the grid; lazy initialisations)
+            ops.propose_sparse_tally = [] if key else None
+            try:
+                res[key] = frames_of(r) + (r.__dict__["_occupancy_hit"][2],)
+            finally:
+                tally, ops.propose_sparse_tally = ops.propose_sparse_tally, None
+        live, total = float(torch.stack([t[0] for t in tally]).sum()), float(sum(t[1] for t in tally))
+        mse = float(torch.nn.functional.mse_loss(res[True][0], res[False][0]))
+        rows.append({"alpha_min": float(alpha_min), "resolution": int(resolution), "cells_occupied": float(res[True][2].occupied),
+                     "coarse_samples_culled": 1. - live / max(total, 1.),
+                     "psnr_sparse_proposal_vs_dense_proposal": float(mse2psnr(mse)) if mse > 0. else float("inf"),
+                     "seconds_per_frame_dense_proposal": res[False][1], "seconds_per_frame_sparse_proposal": res[True][1], "frames": len(mats)})
+        print(json.dumps({"sparse_proposal": rows[-1]}), flush=True)
+    return rows
+
+
 def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=None, eval_epochs=0, eval_dir=None, checkpoint_dir=None,
-        occupancy=None, frozen_eval=True, frozen_occupancy=None, t_min=None, **cfg_kw):
+        occupancy=None, frozen_eval=True, frozen_occupancy=None, t_min=None, sparse_proposal=False, **cfg_kw):
     """-> dict with the per-epoch PSNR / pose-error curve and the loop throughput (+ novel-view scores with eval_epochs > 0)."""
     import dataloading as dl
     from model.common import mse2psnr
@@ -279,6 +346,9 @@ def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=No
     np.random.seed(seed)
     torch.manual_seed(seed)
     cfg = scene_cfg(path, scene, style=style, **cfg_kw)
+    if sparse_proposal and not ((occupancy is not None or frozen_occupancy is not None) and num_fine_of(cfg)
+                                and cfg["rendering"].get("proposal") == "density"):
+        raise ValueError("--sparse-proposal goes with --occupancy or --frozen-occupancy, together with --num-fine and --proposal density")
     loader, fields = dl.get_dataloader(cfg, mode="train", shuffle=True)
     field = fields["img"]
     n_views = field.N_imgs
@@ -320,9 +390,12 @@ def run(path, scene, style="tanks", epochs=100, seed=42, log_every=10, device=No
         import tempfile
         with tempfile.TemporaryDirectory() as tmp:
             novel = novel_view_eval(cfg, trainer.model, pose, field, device, eval_epochs, eval_dir or tmp, n_points=min(1024, n_rays),
-                                    frozen_field=frozen_eval, frozen_occupancy=frozen_occupancy)
+                                    frozen_field=frozen_eval, frozen_occupancy=frozen_occupancy, sparse_proposal=sparse_proposal)
     occ_rows = None
-    if occupancy is not None:      # (resolution, [alpha_min, ...]): dense against sparse evaluation frames
+    if occupancy is not None and sparse_proposal:      # sparse hierarchical frames: the dense proposal against the sparse one
+        occ_rows = sparse_proposal_compare(cfg, trainer.model, pose, loader, field, device, occupancy[0], occupancy[1],
+                                           bounds=[[-1.5, -1.5, -1.], [1.5, 1.5, 1.]] if style == "llff" else None)
+    elif occupancy is not None:      # (resolution, [alpha_min, ...]): dense against sparse evaluation frames
         if num_fine_of(cfg):
             raise ValueError("--occupancy compares plain renders: leave --num-fine off")
         occ_rows = occupancy_compare(cfg, trainer.model, pose, loader, field, device, occupancy[0], occupancy[1],
@@ -358,6 +431,9 @@ def main():
     ap.add_argument("--t-min", type=float, default=None, metavar="T",
                     help="with --occupancy: also render with rendering.occupancy.t_min: T (early ray termination); one more row per ALPHA_MIN "
                          "with the passes run over the sparse render's and the PSNR of the stopped against the dense frames")
+    ap.add_argument("--sparse-proposal", action="store_true",
+                    help="rendering.occupancy.proposal: true (with --occupancy or --frozen-occupancy, --num-fine and --proposal density): the "
+                         "proposal skips known-empty coarse samples; prints the share culled and the PSNR against dense-proposal frames")
     ap.add_argument("--ray-distortion", type=float, default=0.0, metavar="W",
                     help="training.ray_distortion_weight: the weight of the ray distortion of the compositing weights (0 = off; e.g. 0.01)")
     ap.add_argument("--log-every", type=int, default=10)
@@ -376,10 +452,14 @@ def main():
     occupancy = None if a.occupancy is None else (int(a.occupancy[0]), [float(v) for v in a.occupancy[1:]])
     if a.t_min is not None and (occupancy is None or not 0. < a.t_min < 1.):
         ap.error("--t-min T goes with --occupancy and lies in (0, 1)")
+    if a.sparse_proposal and not ((occupancy is not None or a.frozen_occupancy is not None) and a.num_fine > 0 and a.proposal == "density"):
+        ap.error("--sparse-proposal goes with --occupancy or --frozen-occupancy, together with --num-fine F and --proposal density")
+    if a.sparse_proposal and a.t_min is not None:
+        ap.error("--sparse-proposal compares the two proposals: leave --t-min off")
     res = run(a.path, a.scene, style=a.style, epochs=a.epochs, log_every=a.log_every, eval_epochs=a.eval_epochs, eval_dir=a.eval_dir, checkpoint_dir=a.checkpoint_dir, n_rays=a.rays, n_samples=a.samples,
               hidden=a.hidden, resident=not a.host_loader, aux=not a.no_aux, resize_factor=a.factor, workers=a.workers,
               mfma_dtype="bf16" if a.bf16 else "fp32", num_fine=a.num_fine, proposal=a.proposal, occupancy=occupancy,
-              ray_distortion=a.ray_distortion, frozen_eval=not a.no_frozen_eval, t_min=a.t_min,
+              ray_distortion=a.ray_distortion, frozen_eval=not a.no_frozen_eval, t_min=a.t_min, sparse_proposal=a.sparse_proposal,
               frozen_occupancy=None if a.frozen_occupancy is None else (int(a.frozen_occupancy[0]), float(a.frozen_occupancy[1])))
     print(json.dumps({k: v for k, v in res.items() if k != "curve"}))
     if a.out:
