@@ -35,18 +35,49 @@
 //     NNR_F_DIST_ALPHA): its staged density is never read, liveness is never encoded in a density.  resample_row runs on the full row.
 // A culled sample is not evaluated and so cannot make its ray NaN: the one intended difference from the dense kernel.
 // LDS: the dense kernel's + 4 x 256 bytes of lists + 4 counts.
+//
+// NNR_PROPOSE_SPARSE=1 with NNR_PROPOSE_DEPTH=1 compiles this text a third time as depth_sparse_f16_kernel (include/nnr_depth_sparse.h:
+// nnr_render_depth_sparse), a unit of its own: the rendered depth of a ray, (depth, acc), from the live samples alone,
+// stopped per workgroup once its rays are opaque -- to sparse_stop_f16_kernel (nnr_sparse_f16.hip under NNR_SPARSE_STOP=1) what depth_f16_kernel
+// is to the inference forward: no colour branch, no view direction, 8 bytes out per ray.  Without the second define nothing here changes;
+// the second without the first is an error.
+//   * prologue and pass count: the sparse proposal's, without the per-lane depths and liveness bits (no row is staged: the staging rows
+//     keep their place in the LDS map and are not touched).
+//   * passes: the sparse proposal's (the same list, the same sampling, the same NaN rule); a live evaluated sample's raw density is the dense
+//     depth kernel's bit for bit.
+//   * the resampling stage is absent.  Behind each pass stands the sparse render's per-pass compositing (nnr_sparse_f16.hip, the block behind
+//     opt_out4) with `raw` in place of o[3] and the carries cT, cz, cw alone: the delta to the next sample of the ORIGINAL row (recomputed
+//     from z_lo / z_hi / jitter), sample_alpha on half 0, wave_scan_mul of the counted factors, a dead slot's factor 1 and weight 0 by
+//     select.  Those lines are restated here -- this file's own text, as nnr_depth_f16.hip's compositing row is its own: nnr_sparse_f16.hip
+//     shares no header with this unit -- and must stay that block's arithmetic: (depth, acc) are columns 3 and 4 of
+//     nnr_render_sparse_stop bit for bit (tests/test_gpu_depth_sparse.py).
+//   * the stop is sparse_stop_f16_kernel's to the letter: done = 32 (pass + 1) >= n_live || cT < t_min (a NaN carry is never done by
+//     transmittance), s_done[pass & 1][wave], lgkmcnt(0), one raw s_barrier, every wave reads the four flags and leaves together;
+//     vmcnt(0) on every way out of the loop.  t_min = 0: the comparison is never true, the full lists run.
+//   * out[2 r] = wave_sum(cz), out[2 r + 1] = wave_sum(cw) from lane 0 of a wave that has a ray.
+// LDS: the sparse proposal's map + 2 x 4 flags.
 #include "nnr_trunk_f16.h"
 #include "nnr_resample_row.h"
 #include "nnr_cell_rule.h"
 #include "nnr_propose_sparse_kernels.h"
+#include "nnr_depth_sparse_kernels.h"
 
 #ifndef NNR_PROPOSE_SPARSE
 #define NNR_PROPOSE_SPARSE 0
 #endif
+#ifndef NNR_PROPOSE_DEPTH
+#define NNR_PROPOSE_DEPTH 0
+#endif
+#if NNR_PROPOSE_DEPTH && !NNR_PROPOSE_SPARSE
+#error "NNR_PROPOSE_DEPTH=1 is a build of the sparse proposal's text: it needs NNR_PROPOSE_SPARSE=1"
+#endif
 
 namespace nnr {
 
-#if NNR_PROPOSE_SPARSE
+#if NNR_PROPOSE_DEPTH
+#define NNR_PROPOSE_KERNEL depth_sparse_f16_kernel
+typedef DepthSparseArgs ProposeKernelArgs;
+#elif NNR_PROPOSE_SPARSE
 #define NNR_PROPOSE_KERNEL propose_sparse_f16_kernel
 typedef ProposeSparseArgs ProposeKernelArgs;
 #else
@@ -63,8 +94,12 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
     __shared__ uint8_t s_list[kWavesPerBlock][kProposeMaxC];      // per wave: the live samples' indices, increasing
     __shared__ int s_cnt[kWavesPerBlock];                         // per wave: how many
     int n_live = 0;
+#if NNR_PROPOSE_DEPTH
+    __shared__ int s_done[2][kWavesPerBlock];                     // per pass parity and wave: done after that pass (sparse_stop_f16_kernel's)
+#else
     uint32_t live_bits = 0;      // bit k: this lane's sample lane + 64 k is live
     float zk[kRounds];           // the depth of this lane's sample lane + 64 k
+#endif
     {
         const int pl = threadIdx.x & 63, pw = threadIdx.x >> 6;
         const int p_ray_u = blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane(pw);
@@ -75,7 +110,9 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
         const int64_t row0 = (int64_t)p_ray * a.C;
 #pragma unroll
         for (int k = 0; k < kRounds; ++k) {
+#if !NNR_PROPOSE_DEPTH
             zk[k] = 0.f;
+#endif
             if (64 * k < a.C) {
                 const int j = pl + 64 * k;
                 const bool valid = j < a.C;
@@ -95,8 +132,10 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
                 if (lv) s_list[pw][pos] = (uint8_t)j;
                 if (valid && p_has && a.opt_cell) a.opt_cell[row0 + j] = cell;
                 n_live += __popcll(m);
+#if !NNR_PROPOSE_DEPTH
                 live_bits |= lv ? 1u << k : 0u;
                 zk[k] = z;
+#endif
             }
         }
         n_live = __builtin_amdgcn_readfirstlane(n_live);
@@ -108,7 +147,11 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
 #endif
 #include "nnr_density_setup_f16.inc"
     static_assert(kWavesPerBlock * (2 * kProposeMaxC + 2 * kResampleMaxN) <= kRingF4 * 4, "the rows of the resampling stage fit in the weight ring");
+#if NNR_PROPOSE_DEPTH
+    const int C = a.C;
+#else
     const int C = a.C, F = a.F;
+#endif
 #if NNR_PROPOSE_SPARSE
     int n_pass = 0;      // (behind the setup's barrier: the four counts are visible)
 #pragma unroll
@@ -125,9 +168,14 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
     const int wave_ray = blockIdx.x * kWavesPerBlock + wave_u;
     const bool live = wave_ray < a.R;
     const int ray = live ? wave_ray : a.R - 1;
+#if NNR_PROPOSE_DEPTH
+    float cT = 1.f, cz = 0.f, cw = 0.f;      // the compositing carries, across the passes
+    int n_ran = 0;                           // P_g: the passes this workgroup ran
+#else
     float* const s_raw = reinterpret_cast<float*>(smem + kRingF4 + kPark) + wave * (2 * kProposeMaxC);
     float* const s_z = s_raw + kProposeMaxC;
-#if NNR_PROPOSE_SPARSE
+#endif
+#if NNR_PROPOSE_SPARSE && !NNR_PROPOSE_DEPTH
 #pragma unroll
     for (int k = 0; k < kRounds; ++k)      // every depth of the row, culled or not (read behind the barrier that follows the passes)
         if (lane0 + 64 * k < C) s_z[lane0 + 64 * k] = zk[k];
@@ -166,6 +214,51 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
 #include "nnr_density_pass_f16.inc"
     const bool finite_p = fabsf(px) < __uint_as_float(0x7f800000u) && fabsf(py) < __uint_as_float(0x7f800000u) && fabsf(pz) < __uint_as_float(0x7f800000u);
     if (left_f16_range(mx) || !finite_p) raw = __uint_as_float(0x7fc00000u);
+#if NNR_PROPOSE_DEPTH
+    {   // the sparse render's per-pass compositing (nnr_sparse_f16.hip), restated: raw for o[3], the carries cT, cz, cw alone
+        const bool counted = half == 0 && !dead;
+        const int64_t sc = (int64_t)ray * C + j;
+        if (counted && live && a.opt_raw) a.opt_raw[sc] = raw;
+        const int jn = j + 1;
+        float zn = 0.f;
+        if (jn < C) {
+            const float lo1 = a.z_lo[jn], hi1 = a.z_hi[jn];
+            zn = a.jitter ? __fadd_rn(lo1, __fmul_rn(__fsub_rn(hi1, lo1), a.jitter[sc + 1])) : lo1;
+        }
+        float unused;
+        const float alpha = half == 0 ? sample_alpha(raw, jn < C ? zn - z : 1e10f, jn == C, a.flags, unused) : 0.f;
+        const float incl = wave_scan_mul(counted ? (1.f - alpha) + kEpsT : 1.f, lane);      // by select: a dead slot's alpha may be NaN
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 1.f;
+        const float w = counted ? alpha * cT * excl : 0.f;
+        cT *= __shfl(incl, 31, 64);
+        if (counted) { cz += w * z; cw += w; }
+    }
+    pipe.next_pass(pass + 2 < n_pass);
+    {   // the stop (sparse_stop_f16_kernel's): flags by pass parity, one barrier, the same four flags in every wave
+        n_ran = pass + 1;
+        const bool done = kChunk * (pass + 1) >= n_live || cT < a.t_min;      // (cT: the same value in every lane; NaN < t_min is false)
+        if (lane0 == 0) s_done[pass & 1][wave] = done ? 1 : 0;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the flag is written; the next pass's DMA stays in flight
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        int all = 1;
+#pragma unroll
+        for (int w = 0; w < kWavesPerBlock; ++w) all &= s_done[pass & 1][w];
+        if (__builtin_amdgcn_readfirstlane(all)) break;
+    }
+    }   // pass
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // no DMA piece of this wave is in flight past here, stopped early or not
+    if (live && lane0 == 0 && a.opt_passes) a.opt_passes[ray] = n_ran;
+    {
+        const float sz = wave_sum(cz), sw = wave_sum(cw);
+        if (live && lane0 == 0) {
+            a.out[2 * (int64_t)ray] = sz;
+            a.out[2 * (int64_t)ray + 1] = sw;
+        }
+    }
+}
+#else      // ---- the proposal's staging and resampling stage ----
 #if NNR_PROPOSE_SPARSE
     if (half == 0 && !dead) s_raw[j] = raw;      // (its depth is staged already)
 #else
@@ -213,13 +306,19 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
     resample_row(s_z, mm, cdf, fs, out, C, F, a.xi ? a.xi + (int64_t)ray * F : nullptr, a.z_all + (int64_t)ray * (C + F),
                  a.opt_fine ? a.opt_fine + (int64_t)ray * F : nullptr, lane0, live, bad);
 }
+#endif      // NNR_PROPOSE_DEPTH
 
-#if NNR_PROPOSE_SPARSE
+#if NNR_PROPOSE_DEPTH
+hipError_t launch_render_depth_sparse(int D, const DepthSparseArgs& a, hipStream_t st) {
+    if (a.R <= 0 || a.C < 1 || a.C > kProposeMaxC) return hipErrorInvalidValue;
+#elif NNR_PROPOSE_SPARSE
 hipError_t launch_propose_sparse(int D, const ProposeSparseArgs& a, hipStream_t st) {
 #else
 hipError_t launch_propose(int D, const ProposeArgs& a, hipStream_t st) {
 #endif
+#if !NNR_PROPOSE_DEPTH
     if (a.R <= 0 || a.C < 3 || a.C > kProposeMaxC || a.F < 1 || a.C + a.F > kResampleMaxN) return hipErrorInvalidValue;
+#endif
     dim3 grid((a.R + kWavesPerBlock - 1) / kWavesPerBlock), block(256);
     if (D == 256) hipLaunchKernelGGL(NNR_PROPOSE_KERNEL<256>, grid, block, 0, st, a);
     else hipLaunchKernelGGL(NNR_PROPOSE_KERNEL<128>, grid, block, 0, st, a);

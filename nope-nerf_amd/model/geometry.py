@@ -16,6 +16,7 @@
 
 Grid conventions, shared with the kernel: a volume is (nz, ny, nx), x fastest; grid point (ix, iy, iz) sits at origin + step * (ix, iy, iz)
 (fp32: the product rounded, then the sum).  There is no CPU volume path: the density comes from the HIP kernel or not at all."""
+import logging
 import math
 from dataclasses import dataclass
 from typing import Optional
@@ -520,17 +521,28 @@ def projection_rows(camera_mat, world_mat, scale_mat=None):
     return (K @ W @ S)[:, :3, :].reshape(n, 12).to(torch.float32).contiguous()
 
 
-def render_depth_maps(renderer, camera_mat, world_mats, size, min_acc=0.5, chunk=1 << 18, scale_mat=None):
+def render_depth_maps(renderer, camera_mat, world_mats, size, min_acc=0.5, chunk=1 << 18, scale_mat=None, occupancy=None, t_min=0.):
     """The z-depth maps of renderer.model seen from the cameras (camera_mat, world_mats[i]) -> (n, H, W) fp32 on the model's device: what
     nope_nerf(eval_=True) reports as depth, without its colour.  Rays come from nnr.camera.ray_setup on arange_pixels((H, W)), the samples
     from the renderer's own z tables without noise; the rendered distance is divided by ray_norm under rendering.normalise_ray.
     Pixels whose accumulated weight is below min_acc (the phong renderer's tau) become +inf: the ray saw free space; NaN stays NaN.
     With C = num_points - outside_steps <= 256 samples the depth comes from the fused depth kernel (nnr.ops.render_depth: the density alone,
     8 bytes per ray), otherwise from nnr.render_rays' forward-only depth and its per-sample alphas.  chunk: rays per launch.
+    occupancy: an OccupancyGrid of this (frozen) field, the caller's to keep valid.  With it and C <= 256 every chunk goes through the sparse
+    depth kernel (nnr.ops.render_depth_sparse: samples in cells the grid calls empty are not evaluated, a workgroup of four rays stops once
+    each is below the transmittance t_min); with C > 256 the grid is ignored and one logged line says so.  A culled sample is absent from
+    the product, so the maps are the dense ones only as far as the grid's alpha_min is negligible.  t_min (0 <= t_min < 1; 0: off; a
+    ValueError without a grid): stopping drops weight and never adds any, it lowers a ray's acc by less than
+    t_min (1 + C 1e-6 (1 + 1e-6)^C), about t_min, and moves its depth by at most that times the far depth.  Next to min_acc: a pixel whose
+    full acc lies within that margin above min_acc can turn +inf, none turns finite; keep t_min well below min_acc (1e-3 against 0.5).
+    min_acc, normalise_ray and the +inf rule are the same with and without a grid.
     sample_option 'ndc': NotImplementedError -- NDC depths are not world depths.  GPU only."""
     import nnr
     from nnr import camera as _camera
     from .common import arange_pixels
+    t_min = float(t_min)
+    if occupancy is None and t_min != 0.:
+        raise ValueError("render_depth_maps: t_min = %r stops rays in the sparse depth kernel alone, which needs `occupancy`" % (t_min,))
     cfg, net = renderer.cfg, renderer.model
     if cfg['sample_option'] == 'ndc':
         raise NotImplementedError("render_depth_maps: rendering.sample_option 'ndc' samples in NDC space, whose depths are not world depths")
@@ -553,13 +565,20 @@ def render_depth_maps(renderer, camera_mat, world_mats, size, min_acc=0.5, chunk
     dist_alpha, relu_sigma = bool(cfg['dist_alpha']), net.occ_activation != 'softplus'
     pixels = arange_pixels((H, W), device=dev)[1]                                          # (1, H W, 2), row-major
     out = torch.empty(n, H * W, **f32)
+    if occupancy is not None and n_samples > 256:
+        logging.getLogger(__name__).info("render_depth_maps: occupancy grid ignored, dense render: %d samples per ray, the sparse depth kernel "
+                                         "takes at most 256", n_samples)
     with torch.no_grad():
         z_lo, z_hi = renderer._z_tables(n_samples, renderer.depth_range[0], renderer.depth_range[1], False, dev)
         for i in range(n):
             origin, ray, view, ray_norm, _, _ = _camera.ray_setup(pixels, None, K, world_mats[i:i + 1], S, normalise, use_dir)
             for r0 in range(0, H * W, int(chunk)):
                 sl = slice(r0, min(r0 + int(chunk), H * W))
-                if n_samples <= 256:
+                if n_samples <= 256 and occupancy is not None:
+                    da = _nnr_ops.render_depth_sparse(origin[sl], ray[sl], z_lo, z_hi, None, occupancy, w, b, hidden=net.hidden_dim,
+                                                      dist_alpha=dist_alpha, relu_sigma=relu_sigma, t_min=t_min)
+                    depth, acc = da[:, 0], da[:, 1]
+                elif n_samples <= 256:
                     da = _nnr_ops.render_depth(origin[sl], ray[sl], z_lo, z_hi, None, w, b, hidden=net.hidden_dim, dist_alpha=dist_alpha,
                                                relu_sigma=relu_sigma)
                     depth, acc = da[:, 0], da[:, 1]
@@ -620,7 +639,7 @@ def _dense_from_bricks(values, dims):
 
 
 def extract_mesh_tsdf(renderer, cameras, lo, hi, resolution, refine=None, trunc_voxels=3, dilate=1, colour=True, integrate=None,
-                      depth_maps=None, min_acc=0.5, chunk=65536, max_bricks=None):
+                      depth_maps=None, min_acc=0.5, chunk=65536, max_bricks=None, occupancy=None, t_min=0.):
     """The zero set of the truncated signed distance volume fused from the model's rendered depth maps of `cameras` (a Cameras) inside the box
     [lo, hi], as a Mesh at level 0 (Curless-Levoy with weight 1 per observation): what the model was trained on -- the rendered depth of
     its learned cameras -- and not a level of the raw density.  `inside` (positive) is behind the surfaces the cameras saw.
@@ -633,7 +652,8 @@ def extract_mesh_tsdf(renderer, cameras, lo, hi, resolution, refine=None, trunc_
       trunc_voxels  the truncation distance in steps of the grid that is being integrated (the largest |step| of its three): the coarse
                     volume is truncated at trunc_voxels coarse steps, the fine bricks at trunc_voxels fine steps.
       depth_maps    (n,H,W) z-depth maps on the integrator's device where the caller has them, or a callable () -> such maps (a timer's
-                    hook); None: render_depth_maps(renderer, ...) with min_acc.
+                    hook); None: render_depth_maps(renderer, ...) with min_acc, occupancy and t_min (an OccupancyGrid of the frozen field
+                    and the stop's transmittance: the sparse depth kernel, see there).
       integrate     a callable (origin, step, bricks, cams, depth, trunc, sum, weight) that stands in for nnr.ops.tsdf_integrate (the CPU
                     tests' reference integrator, a timer's hook); with it and depth_maps the host side runs anywhere, normals and colours
                     are then made only where a renderer on the GPU is given as well.
@@ -649,7 +669,8 @@ def extract_mesh_tsdf(renderer, cameras, lo, hi, resolution, refine=None, trunc_
         integrate = lambda o, s, br, cm, dp, tr, sm, wt: _nnr_ops.tsdf_integrate(o, s, br, cm, dp, tr, sm, wt)
     with torch.no_grad():
         if depth_maps is None:
-            depth = render_depth_maps(renderer, cameras.camera_mat, cameras.world_mats, cameras.size, min_acc=min_acc, scale_mat=cameras.scale_mat)
+            depth = render_depth_maps(renderer, cameras.camera_mat, cameras.world_mats, cameras.size, min_acc=min_acc, scale_mat=cameras.scale_mat,
+                                      occupancy=occupancy, t_min=t_min)
         else:
             depth = depth_maps() if callable(depth_maps) else depth_maps
         depth = depth.detach().to(torch.float32).contiguous()

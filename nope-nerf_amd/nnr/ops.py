@@ -948,3 +948,42 @@ def propose_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor,
     if tally is not None:
         tally.append((count.sum(), R * Cn))
     return (z_all, alpha_c, z_c, fine, count, cell, passes) if debug else z_all
+
+
+depth_sparse_tally = None      # tools: while this is a list, every render_depth_sparse call appends (live samples (1), passes summed over rays (1), R C, R)
+
+
+def render_depth_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor, jitter: Optional[torch.Tensor], grid,
+                        weights, biases, *, hidden: int, dist_alpha: bool, relu_sigma: bool, t_min: float = 0.0, debug: bool = False):
+    """render_depth that does not evaluate the samples an occupancy grid calls empty and stops a workgroup of four rays once they are opaque,
+    in one launch of nnr_render_depth_sparse (include/nnr_depth_sparse.h): render_depth's inputs plus `grid`, as render_sparse takes it ->
+    (R,2) fp32, (depth, acc) per ray over the evaluated samples -- bit for bit the dist and acc render_sparse(..., t_min=t_min) gives the
+    same rays, without its colour branch, view direction and rgb.  A ray without a live sample gets (0, 0); a culled or unevaluated sample
+    cannot make its ray NaN.  t_min (0 <= t_min < 1; 0: the full lists run): as render_sparse's.  The cached pack, as propose.
+    debug: (out, raw (R,C) pre-filled with NaN and written at the evaluated samples alone, count (R) int32, cell (R,C) int32, passes (R)
+    int32).  Any R, 1 <= C <= 256.  Not differentiable.  No host synchronisation."""
+    t_min = float(t_min)
+    if not 0.0 <= t_min < 1.0:      # (a NaN fails)
+        raise ValueError("render_depth_sparse: t_min must be in [0, 1); got %r" % (t_min,))
+    _require_gpu(pts_o)
+    R, Cn = pts_o.shape[0], z_lo.shape[0]
+    dev = pts_o.device
+    cfg = split2_cfg(R, Cn, hidden, dist_alpha=dist_alpha, relu_sigma=relu_sigma)
+    (pts_o, pts_d), z_lo, z_hi, jit = _ray_inputs((pts_o, pts_d), z_lo, z_hi, jitter)
+    lo3, is3, d3, bits = _grid_args(grid, dev, "render_depth_sparse")
+    packed = _packed_for(cfg, list(weights), list(biases))
+    out = torch.empty(R, 2, dtype=torch.float32, device=dev)
+    raw = count = cell = passes = None
+    if debug:
+        raw = torch.full((R, Cn), float("nan"), dtype=torch.float32, device=dev)
+        count, passes = torch.empty(R, dtype=torch.int32, device=dev), torch.empty(R, dtype=torch.int32, device=dev)
+        cell = torch.empty(R, Cn, dtype=torch.int32, device=dev)
+    tally = depth_sparse_tally
+    if tally is not None and not debug:
+        count, passes = torch.empty(R, dtype=torch.int32, device=dev), torch.empty(R, dtype=torch.int32, device=dev)
+    L.check(L.load().nnr_render_depth_sparse(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), lo3, is3, d3,
+                                             L.ptr(bits), t_min, L.ptr(packed), L.ptr(out), L.ptr(raw), L.ptr(count), L.ptr(cell),
+                                             L.ptr(passes), L.stream()), "nnr_render_depth_sparse")
+    if tally is not None:
+        tally.append((count.sum(), passes.sum(), R * Cn, R))
+    return (out, raw, count, cell, passes) if debug else out

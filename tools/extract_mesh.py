@@ -3,7 +3,8 @@
     python tools/extract_mesh.py <config.yaml> [--default configs/default.yaml] [--resolution 256] [--lo X Y Z --hi X Y Z]
                                  [--level RAW] [--no-colour] [--slab LAYERS] [--out mesh.ply]
                                  [--refine {2,4,8} [--dilate N] [--max-bricks B]]
-                                 [--method tsdf [--every N] [--trunc-voxels T] [--min-acc A]]
+                                 [--method tsdf [--every N] [--trunc-voxels T] [--min-acc A]
+                                                [--occupancy RES ALPHA_MIN [--occupancy-dilate N] [--occupancy-bounds LO HI] [--t-min T]]]
 
 The checkpoint is found the way the image-extraction script finds it (vis/render.py of the upstream project, which runs against these
 packages): the config layered over the defaults, OfficialStaticNerf + Renderer + get_model, CheckpointIO(training.out_dir).load(
@@ -20,7 +21,15 @@ dense fine grid, both kernels' times between device events, and the peak device 
 depth maps (geometry.extract_mesh_tsdf), seen from every --every'th frame of the training split at the learned
 poses of model_pose.pt (and the learned focal of model_focal.pt where pose.learn_focal is set), the way the image-extraction scripts build
 their cameras.  --resolution, --refine, --dilate, --max-bricks, --lo / --hi and --no-colour apply; --level and --slab do not.  Prints the
-number of cameras, the time of the depth renders and of the fusion launches between device events, bricks, vertices and peak memory."""
+number of cameras, the time of the depth renders and of the fusion launches between device events, bricks, vertices and peak memory.
+
+--occupancy RES ALPHA_MIN (with --method tsdf): the depth maps come from the sparse depth kernel
+(geometry.render_depth_maps(occupancy=grid, t_min=T): nnr.ops.render_depth_sparse).  The flags become rendering.occupancy {resolution,
+alpha_min, dilate, bounds} and the grid is built once with renderer.frozen_occupancy_grid: the checkpoint is a frozen field, this tool owns
+the grid.  --t-min T (0 < T < 1, with --occupancy): a workgroup of four rays stops once each is below that transmittance.  No default
+alpha_min or t_min is shipped.  For the first fused frame the tool prints the grid's occupied share, the mean share of live samples and
+of passes run, the largest and median |depth_sparse - depth_dense| over the pixels finite in both and the number of pixels whose +inf
+status differs: one extra dense frame."""
 import argparse
 import os
 import sys
@@ -81,6 +90,17 @@ def tsdf(args, G, renderer, cfg, scalars, lo, hi):
     cams = load_cameras(cfg, device, args.every)
     n_cams, (H, W) = cams.world_mats.shape[0], cams.size
     G.render_depth_maps(renderer, cams.camera_mat, cams.world_mats[:1], (2, 2))      # loads the code object, packs the weights
+    grid, t_min = None, 0. if args.t_min is None else args.t_min
+    if args.occupancy is not None:
+        occ = {"resolution": int(args.occupancy[0]), "alpha_min": float(args.occupancy[1]), "dilate": args.occupancy_dilate}
+        if args.occupancy_bounds is not None:
+            occ["bounds"] = [float(v) for v in args.occupancy_bounds]
+        cfg['rendering']['occupancy'] = renderer.cfg['occupancy'] = occ
+        grid = renderer.frozen_occupancy_grid(device)      # built once: the checkpoint is a frozen field, the grid is this tool's
+        if grid is None:
+            sys.exit("extract_mesh: rendering.occupancy %r gives no grid for this config (see the logged reason)" % (occ,))
+        first = occupancy_report(G, ops, renderer, cams, grid, t_min, args.min_acc)
+    torch.cuda.synchronize()
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     ev = lambda: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -88,7 +108,7 @@ def tsdf(args, G, renderer, cfg, scalars, lo, hi):
 
     def depth_maps():
         render_ev[0].record()
-        d = G.render_depth_maps(renderer, cams.camera_mat, cams.world_mats, (H, W), min_acc=args.min_acc)
+        d = G.render_depth_maps(renderer, cams.camera_mat, cams.world_mats, (H, W), min_acc=args.min_acc, occupancy=grid, t_min=t_min)
         render_ev[1].record()
         return d
 
@@ -112,13 +132,61 @@ def tsdf(args, G, renderer, cfg, scalars, lo, hi):
     ms_f = sum(a.elapsed_time(b) for a, b in fuse_ev)
     print("checkpoint: it %s" % scalars.get('it', '?'))
     print("cameras: %d of %d x %d (every %d), %d samples per ray, min acc %g" % (n_cams, H, W, args.every, samples, args.min_acc))
-    print("depth renders: %.3f ms (%.3f ns per sample)" % (ms_r, ms_r * 1e6 / (n_cams * H * W * samples)))
+    print("depth renders: %.3f ms (%.3f ns per sample)%s" % (ms_r, ms_r * 1e6 / (n_cams * H * W * samples),
+                                                           "" if grid is None else ", sparse depth kernel, t_min %g" % t_min))
+    if grid is not None:
+        print("occupancy: %s, first frame: %s" % (occ, first))
     print("fusion: %d launches, %.3f ms (%.4f ns per voxel-camera pair), truncation %g voxels" % (len(fuse_ev), ms_f, ms_f * 1e6 / max(1, pairs[0]),
                                                                                             args.trunc_voxels))
     print("grid: %d x %d x %d in [%s] .. [%s]%s, %d bricks" % (tuple(mesh.dims) + (", ".join("%g" % v for v in lo), ", ".join("%g" % v for v in hi),
                                                                                   ", refined %d times" % r if r else "", mesh.n_bricks)))
     print("peak device memory: %.1f MB" % (peak / 1e6))
     print("mesh: %d vertices, %d quads = %d triangles -> %s" % (mesh.vertices.shape[0], mesh.quads.shape[0], 2 * mesh.quads.shape[0], out))
+
+
+def check_occupancy_args(ap, args):
+    """--occupancy and its companions go with --method tsdf, the companions with --occupancy; no GPU is needed to say so"""
+    given = [n for n, v in (("--occupancy", args.occupancy), ("--occupancy-dilate", args.occupancy_dilate),
+                            ("--occupancy-bounds", args.occupancy_bounds), ("--t-min", args.t_min)) if v is not None]
+    if given and args.method != "tsdf":
+        ap.error("%s: with --method tsdf only" % ", ".join(given))
+    if given and args.occupancy is None:
+        ap.error("%s: with --occupancy RES ALPHA_MIN only" % ", ".join(given))
+    if args.occupancy is not None:
+        try:
+            ok = int(args.occupancy[0]) >= 1 and float(args.occupancy[1]) == float(args.occupancy[1])
+        except ValueError:
+            ok = False
+        if not ok:
+            ap.error("--occupancy RES ALPHA_MIN: a cell count and an alpha")
+        if args.occupancy_dilate is None:
+            args.occupancy_dilate = 1
+        if args.occupancy_dilate < 0:
+            ap.error("--occupancy-dilate N: a cell count >= 0")
+    if args.t_min is not None and not 0. < args.t_min < 1.:
+        ap.error("--t-min T lies in (0, 1)")
+
+
+def occupancy_report(G, ops, renderer, cams, grid, t_min, min_acc):
+    """The first fused frame through the sparse depth kernel and once dense -> what --occupancy prints about it"""
+    samples = int(renderer.cfg['num_points']) - int(renderer.cfg['outside_steps'])
+    ops.depth_sparse_tally = []
+    try:
+        sparse = G.render_depth_maps(renderer, cams.camera_mat, cams.world_mats[:1], cams.size, min_acc=min_acc, occupancy=grid, t_min=t_min)
+        tally = ops.depth_sparse_tally
+    finally:
+        ops.depth_sparse_tally = None
+    dense = G.render_depth_maps(renderer, cams.camera_mat, cams.world_mats[:1], cams.size, min_acc=min_acc)
+    res = {"cells_occupied": round(float(grid.occupied), 6)}
+    if tally:      # (none above 256 samples per ray: the dense render ran)
+        live, passes = sum(float(t[0]) for t in tally), sum(float(t[1]) for t in tally)
+        total, rays = sum(t[2] for t in tally), sum(t[3] for t in tally)
+        res.update(samples_live=round(live / total, 6), passes_run=round(passes / rays, 4), passes_full=(samples + 31) // 32)
+    both = torch.isfinite(sparse) & torch.isfinite(dense)
+    diff = (sparse - dense)[both].abs()
+    res.update(depth_diff_max=float(diff.max()) if diff.numel() else None, depth_diff_median=float(diff.median()) if diff.numel() else None,
+               inf_status_differs=int((torch.isinf(sparse) != torch.isinf(dense)).sum()), pixels=int(sparse.numel()))
+    return res
 
 
 def main():
@@ -140,7 +208,16 @@ def main():
     ap.add_argument("--every", type=int, default=1, help="with --method tsdf: fuse every N'th training frame")
     ap.add_argument("--trunc-voxels", type=float, default=3., help="with --method tsdf: the truncation distance in grid steps")
     ap.add_argument("--min-acc", type=float, default=0.5, help="with --method tsdf: a pixel whose accumulated weight is below this saw free space")
+    ap.add_argument("--occupancy", nargs=2, default=None, metavar=("RES", "ALPHA_MIN"),
+                    help="with --method tsdf: render the depth maps through the sparse depth kernel with an occupancy grid of RES cells per "
+                         "axis, a cell empty where the alpha at the coarse sample spacing stays below ALPHA_MIN (rendering.occupancy)")
+    ap.add_argument("--occupancy-dilate", type=int, default=None, metavar="N", help="with --occupancy: cells kept around an occupied one (default 1)")
+    ap.add_argument("--occupancy-bounds", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="with --occupancy: the grid's box on every axis (default: the cube of rendering.radius)")
+    ap.add_argument("--t-min", type=float, default=None, metavar="T",
+                    help="with --occupancy: stop a workgroup of four rays once each is below this transmittance, 0 < T < 1")
     args = ap.parse_args()
+    check_occupancy_args(ap, args)
     if not torch.cuda.is_available():
         sys.exit("extract_mesh: needs a GPU (the density volume comes from the HIP grid kernel; there is no CPU volume path)")
     from model import geometry as G
