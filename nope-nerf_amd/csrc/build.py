@@ -24,7 +24,10 @@ SOURCES = [("nnr_mlp_fwd.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=1", "NNR_FWD_MOD
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=256", "NNR_FWD_TRAIN=3")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_STASH=0", "NNR_DGRAD_LIST=1")),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=3")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=128", "NNR_DGRAD_STASH=0", "NNR_DGRAD_LIST=1")),
            ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1")), ("nnr_mlp_dgrad_f16.hip", ("NNR_DGRAD_D=128",)),
-           ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_sparse_f16.hip", ()), ("nnr_sparse_f16.hip", ("NNR_SPARSE_STOP=1",)), ("nnr_march_f16.hip", ()), ("nnr_propose_f16.hip", ()), ("nnr_propose_f16.hip", ("NNR_PROPOSE_SPARSE=1",)), ("nnr_propose_f16.hip", ("NNR_PROPOSE_SPARSE=1", "NNR_PROPOSE_DEPTH=1")), ("nnr_grid_f16.hip", ()), ("nnr_bricks_f16.hip", ()),
+           ("nnr_mlp_fwd_f16.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0")), ("nnr_sparse_f16.hip", ()), ("nnr_sparse_f16.hip", ("NNR_SPARSE_STOP=1",)), ("nnr_march_f16.hip", ()), ("nnr_propose_f16.hip", ()), ("nnr_propose_f16.hip", ("NNR_PROPOSE_SPARSE=1",)), ("nnr_propose_f16.hip", ("NNR_PROPOSE_SPARSE=1", "NNR_PROPOSE_DEPTH=1")),
+           # the quantile-depth builds of the two depth kernels (include/nnr_depth_median.h)
+           ("nnr_propose_f16.hip", ("NNR_PROPOSE_SPARSE=1", "NNR_PROPOSE_DEPTH=2")), ("nnr_depth_f16.hip", ("NNR_DEPTH_MEDIAN=1",)),
+           ("nnr_grid_f16.hip", ()), ("nnr_bricks_f16.hip", ()),
            ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=256", "NNR_DGRAD_MODE=2")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=1", "NNR_FWD_MODE=2")), ("nnr_mlp_dgrad.hip", ("NNR_DGRAD_D=128", "NNR_DGRAD_MODE=2")),
            ("nnr_mlp_fwd.hip", ("NNR_FWD_D=128", "NNR_FWD_TRAIN=0", "NNR_FWD_MODE=2")),
@@ -66,7 +69,9 @@ SCRATCH_LIMIT = {"18mlp_fwd_f16_kernelI": 0, "18mlp_fwd_f16_kernelILi256ELb0E": 
                  "17sparse_f16_kernelI": 48,      # (the inference forward's passes and composite carry: its allowance)
                  "22sparse_stop_f16_kernelI": 48,      # (the same text under NNR_SPARSE_STOP=1: include/nnr_sparse_stop.h)
                  "25propose_sparse_f16_kernelI": 0,      # (the proposal's text under NNR_PROPOSE_SPARSE=1: include/nnr_propose_sparse.h)
-                 "23depth_sparse_f16_kernelI": 0}      # (the same text under NNR_PROPOSE_SPARSE=1 NNR_PROPOSE_DEPTH=1: include/nnr_depth_sparse.h)
+                 "23depth_sparse_f16_kernelI": 0,      # (the same text under NNR_PROPOSE_SPARSE=1 NNR_PROPOSE_DEPTH=1: include/nnr_depth_sparse.h)
+                 "23depth_median_f16_kernelI": 0,      # (the depth kernel's text under NNR_DEPTH_MEDIAN=1: include/nnr_depth_median.h)
+                 "30depth_sparse_median_f16_kernelI": 0}      # (the sparse depth build under NNR_PROPOSE_DEPTH=2: include/nnr_depth_median.h)
 
 
 def check_resources(remarks, what):

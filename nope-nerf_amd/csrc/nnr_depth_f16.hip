@@ -16,13 +16,33 @@
 // in the proposal kernel; a ray with a NaN alpha or z gets (NaN, NaN), and no other ray of its workgroup is touched.
 // LDS: the weight ring (3 panels, 96 KB), the park area (32 KB), the tables, and the staging: 2 x 256 floats per wave (8 KB).
 // The compositing row is this file's own text: nnr_resample_row.h belongs to the resample and proposal units.
+//
+// NNR_DEPTH_MEDIAN=1 compiles this text a second time as depth_median_f16_kernel (include/nnr_depth_median.h: nnr_render_depth_median;
+// DESIGN.md section 11.4), a unit of its own: (depth, acc, q) per ray, q the depth at which the transmittance falls below a.level.  Without
+// the define nothing here changes.  The passes and the first two columns are untouched; in the second loop of the epilogue a lane has the
+// transmittance in front of and behind each sample of its run (the products the weights are made of): the first sample i of the run with
+// T_{i+1} < level (a NaN never crosses) gives the lane's q = z_i + (z_next - z_i) ((T_i - level) / (T_i - T_{i+1})), z_next the depth of
+// sample i + 1 (z_i behind the last), every operation rounded to fp32, one IEEE division.  Runs are contiguous and increase with the lane:
+// one ballot, the lowest lane that crossed, its q broadcast.  No crossing: +inf, NaN where the row's product is NaN; a `bad` ray: NaN.
 #include "nnr_trunk_f16.h"
 #include "nnr_fusion_kernels.h"
 
+#ifndef NNR_DEPTH_MEDIAN
+#define NNR_DEPTH_MEDIAN 0
+#endif
+
 namespace nnr {
 
+#if NNR_DEPTH_MEDIAN
+#define NNR_DEPTH_KERNEL depth_median_f16_kernel
+typedef DepthMedianArgs DepthKernelArgs;
+#else
+#define NNR_DEPTH_KERNEL depth_f16_kernel
+typedef DepthArgs DepthKernelArgs;
+#endif
+
 template <int D>
-__global__ __launch_bounds__(256, 1) void depth_f16_kernel(DepthArgs a) {
+__global__ __launch_bounds__(256, 1) void NNR_DEPTH_KERNEL(DepthKernelArgs a) {
     constexpr int kDensityExtraF4 = kWavesPerBlock * 2 * kProposeMaxC / 4;      // per wave the raw densities and the depths of its ray
 #include "nnr_density_setup_f16.inc"
     const int C = a.C;
@@ -91,27 +111,61 @@ __global__ __launch_bounds__(256, 1) void depth_f16_kernel(DepthArgs a) {
     float T = __shfl_up(incl, 1, 64);
     if (lane0 == 0) T = 1.f;
     float sd = 0.f, sw = 0.f;
+#if NNR_DEPTH_MEDIAN
+    bool crossed = false;      // this lane's run holds a crossing; q: of the first one
+    float q = 0.f;
+#endif
     for (int i = i0; i < i1; ++i) {
         const float al = s_raw[i];
         const float w = al * T;
         sd += w * s_z[i];
         sw += w;
+#if NNR_DEPTH_MEDIAN
+        const float T0 = T;
+#endif
         T *= (1.f - al) + kEpsT;
+#if NNR_DEPTH_MEDIAN
+        if (!crossed && T < a.level) {      // (a NaN never crosses)
+#pragma clang fp contract(off)      // (this block: every operation of q is rounded on its own)
+            const float zm = s_z[i], zn = i + 1 < C ? s_z[i + 1] : zm;
+            q = zm + (zn - zm) * ((T0 - a.level) / (T0 - T));
+            crossed = true;
+        }
+#endif
     }
     sd = wave_sum(sd);
     sw = wave_sum(sw);
+#if NNR_DEPTH_MEDIAN
+    {   // the first crossing of the row is the lowest lane's that has one; without one the row's product (lane 63 ends with it) decides
+        const uint64_t who = __ballot(crossed);
+        const float Tc = __shfl(T, 63, 64);
+        const float qc = __shfl(q, who ? __ffsll((unsigned long long)who) - 1 : 0, 64);
+        q = who ? qc : (Tc == Tc ? __uint_as_float(0x7f800000u) : __uint_as_float(0x7fc00000u));
+    }
+    if (live && lane0 == 0) {
+        const float qnan = __uint_as_float(0x7fc00000u);
+        a.out[3 * (int64_t)ray] = bad ? qnan : sd;
+        a.out[3 * (int64_t)ray + 1] = bad ? qnan : sw;
+        a.out[3 * (int64_t)ray + 2] = bad ? qnan : q;
+    }
+#else
     if (live && lane0 == 0) {
         const float qnan = __uint_as_float(0x7fc00000u);
         a.out[2 * (int64_t)ray] = bad ? qnan : sd;
         a.out[2 * (int64_t)ray + 1] = bad ? qnan : sw;
     }
+#endif
 }
 
+#if NNR_DEPTH_MEDIAN
+hipError_t launch_render_depth_median(int D, const DepthMedianArgs& a, hipStream_t st) {
+#else
 hipError_t launch_render_depth(int D, const DepthArgs& a, hipStream_t st) {
+#endif
     if (a.R <= 0 || a.C < 1 || a.C > kProposeMaxC) return hipErrorInvalidValue;
     dim3 grid(((uint32_t)a.R + kWavesPerBlock - 1) / kWavesPerBlock), block(256);
-    if (D == 256) hipLaunchKernelGGL(depth_f16_kernel<256>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(depth_f16_kernel<128>, grid, block, 0, st, a);
+    if (D == 256) hipLaunchKernelGGL(NNR_DEPTH_KERNEL<256>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(NNR_DEPTH_KERNEL<128>, grid, block, 0, st, a);
     return hipGetLastError();
 }
 

@@ -28,7 +28,13 @@ struct DepthSparseArgs {
     uint32_t flags;               // NNR_F_RELU_SIGMA / NNR_F_DIST_ALPHA
 };
 
+// the same render with the quantile depth beside (nnr_propose_f16.hip under NNR_PROPOSE_DEPTH=2; include/nnr_depth_median.h)
+struct DepthSparseMedianArgs : DepthSparseArgs {      // out: (R,3): depth, acc, q
+    float level;                  // q: the depth at which the transmittance falls below this; 0 < level < 1, t_min <= level
+};
+
 hipError_t launch_render_depth_sparse(int D, const DepthSparseArgs& a, hipStream_t st);      // nnr_propose_f16.hip under NNR_PROPOSE_DEPTH=1
+hipError_t launch_render_depth_sparse_median(int D, const DepthSparseMedianArgs& a, hipStream_t st);      // the same under NNR_PROPOSE_DEPTH=2
 
 // nnr_api.cpp: what a launcher returned -> the entry point's return code (NNR_E_HIP, the HIP error kept for nnr_last_hip_error)
 int launched(hipError_t e);

@@ -1,4 +1,5 @@
-// nnr_fusion_api.cpp -- the extern "C" entry points of include/nnr_fusion.h (the depth-fusion side of the geometry export): argument checking
+// nnr_fusion_api.cpp -- the extern "C" entry points of include/nnr_fusion.h (the depth-fusion side of the geometry export) and the dense entry
+// of include/nnr_depth_median.h (the same depth render with the quantile depth beside): argument checking
 // and marshalling into the two kernels' argument structs (nnr_fusion_kernels.h).  A host unit of its own: nnr_api.cpp keeps nnr.h's and
 // nnr_geometry.h's sets.  Every error return is decided before any device work -- no pointer is dereferenced here except the host arrays
 // `origin` and `step` -- and every call is asynchronous on the caller's stream.  No state: the last HIP error is nnr_api.cpp's (launched).
@@ -7,6 +8,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "../../include/nnr_depth_median.h"
 #include "../../include/nnr_fusion.h"
 #include "nnr_fusion_kernels.h"
 
@@ -36,6 +38,27 @@ int nnr_render_depth(const nnr_cfg* cfg, const float* pts_o, const float* pts_d,
     a.R = cfg->n_rays; a.C = cfg->n_samples;
     a.flags = cfg->flags & (NNR_F_RELU_SIGMA | NNR_F_DIST_ALPHA);
     return launched(launch_render_depth(cfg->hidden, a, (hipStream_t)stream));
+}
+
+// nnr_render_depth's checks in their order; `level` is a value: it is refused with the sizes and the null pointers
+int nnr_render_depth_median(const nnr_cfg* cfg, const float* pts_o, const float* pts_d, const float* z_lo, const float* z_hi, const float* jitter,
+                            float level, const float* packed, float* out, float* opt_raw, float* opt_z, void* stream) {
+    if (!cfg || cfg->n_rays < 1 || cfg->n_samples < 1) return NNR_E_BADCFG;
+    if (!pts_o || !pts_d || !z_lo || !z_hi || !packed || !out) return NNR_E_BADCFG;      // (jitter and the opt_* may be null)
+    if (!(level > 0.f && level < 1.f)) return NNR_E_BADCFG;      // (a NaN fails both comparisons)
+    if (cfg->n_samples > 256 || (cfg->hidden != 128 && cfg->hidden != 256)) return NNR_E_UNSUPPORTED;
+    if ((cfg->flags & (NNR_F_BF16 | NNR_F_SPLIT3 | NNR_F_SPLIT2)) != (NNR_F_SPLIT3 | NNR_F_SPLIT2) || (cfg->flags & NNR_F_TRAIN)) return NNR_E_UNSUPPORTED;
+    if (!aligned(packed, 16)) return NNR_E_ALIGN;
+    for (const void* p : {(const void*)pts_o, (const void*)pts_d, (const void*)z_lo, (const void*)z_hi, (const void*)jitter, (const void*)out,
+                          (const void*)opt_raw, (const void*)opt_z})
+        if (!aligned(p, 4)) return NNR_E_ALIGN;
+    DepthMedianArgs a{};
+    a.pts_o = pts_o; a.pts_d = pts_d; a.z_lo = z_lo; a.z_hi = z_hi; a.jitter = jitter; a.packed = packed;
+    a.out = out; a.opt_raw = opt_raw; a.opt_z = opt_z;
+    a.R = cfg->n_rays; a.C = cfg->n_samples;
+    a.flags = cfg->flags & (NNR_F_RELU_SIGMA | NNR_F_DIST_ALPHA);
+    a.level = level;
+    return launched(launch_render_depth_median(cfg->hidden, a, (hipStream_t)stream));
 }
 
 int nnr_tsdf_integrate(const float origin[3], const float step[3], const int32_t* bricks, int32_t n_bricks, const float* cams, int32_t n_cams,

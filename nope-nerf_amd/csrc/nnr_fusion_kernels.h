@@ -19,6 +19,11 @@ struct DepthArgs {
     uint32_t flags;               // NNR_F_RELU_SIGMA / NNR_F_DIST_ALPHA
 };
 
+// the same render with the quantile depth beside (nnr_depth_f16.hip under NNR_DEPTH_MEDIAN=1; include/nnr_depth_median.h)
+struct DepthMedianArgs : DepthArgs {      // out: (R,3): (depth, acc, q)
+    float level;                  // q: the depth at which the transmittance falls below this; 0 < level < 1
+};
+
 // the integration of depth maps into a truncated signed distance volume held in 8 x 8 x 8 bricks (nnr_tsdf.hip)
 struct TsdfArgs {
     const int32_t* bricks;        // (B,3): (bx, by, bz)
@@ -35,6 +40,7 @@ struct TsdfArgs {
 constexpr int kTsdfMaxExtent = 1 << 24;      // W, H: every pixel index is an exact fp32
 
 hipError_t launch_render_depth(int D, const DepthArgs& a, hipStream_t st);      // nnr_depth_f16.hip
+hipError_t launch_render_depth_median(int D, const DepthMedianArgs& a, hipStream_t st);      // nnr_depth_f16.hip under NNR_DEPTH_MEDIAN=1
 hipError_t launch_tsdf_integrate(const TsdfArgs& a, hipStream_t st);            // nnr_tsdf.hip
 
 // nnr_api.cpp: what a launcher returned -> the entry point's return code (NNR_E_HIP, the HIP error kept for nnr_last_hip_error)

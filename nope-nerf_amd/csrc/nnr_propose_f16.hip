@@ -56,6 +56,17 @@
 //     vmcnt(0) on every way out of the loop.  t_min = 0: the comparison is never true, the full lists run.
 //   * out[2 r] = wave_sum(cz), out[2 r + 1] = wave_sum(cw) from lane 0 of a wave that has a ray.
 // LDS: the sparse proposal's map + 2 x 4 flags.
+//
+// NNR_PROPOSE_DEPTH=2 (with NNR_PROPOSE_SPARSE=1) compiles the depth build once more as depth_sparse_median_f16_kernel
+// (include/nnr_depth_median.h: nnr_render_depth_median_sparse): (depth, acc, q), q the depth at which the ray's
+// transmittance falls below a.level.  Everything under `#if NNR_PROPOSE_DEPTH` holds for both values; the lines of this build alone stand
+// under `== 2`: a wave-uniform `found` and the carry q.  Per pass a counted lane has T in front of its sample, cT excl, and behind it,
+// cT incl (cT: the carry of the earlier passes); the first counted lane with cT incl < level while `found` is still false gives
+// q = z + (z_next - z) ((cT excl - level) / (cT excl - cT incl)), z_next the neighbour alpha's delta uses (z behind the last sample of
+// the row), every operation rounded on its own (fp contract off), one IEEE division; list order is lane order: ballot, then readlane.  That
+// block sits in front of the carry's update and outside the stop's barrier region; the stop rule, the flags, the barrier and the opt_*
+// are the depth build's.  Once cT < level a crossing has been found, so t_min <= level (the host entry refuses more) stops no ray in
+// front of its crossing: q is the t_min = 0 one bit for bit.  No crossing: +inf, NaN where the carry is NaN.  LDS: the depth build's.
 #include "nnr_trunk_f16.h"
 #include "nnr_resample_row.h"
 #include "nnr_cell_rule.h"
@@ -74,7 +85,10 @@
 
 namespace nnr {
 
-#if NNR_PROPOSE_DEPTH
+#if NNR_PROPOSE_DEPTH == 2
+#define NNR_PROPOSE_KERNEL depth_sparse_median_f16_kernel
+typedef DepthSparseMedianArgs ProposeKernelArgs;
+#elif NNR_PROPOSE_DEPTH
 #define NNR_PROPOSE_KERNEL depth_sparse_f16_kernel
 typedef DepthSparseArgs ProposeKernelArgs;
 #elif NNR_PROPOSE_SPARSE
@@ -171,6 +185,10 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
 #if NNR_PROPOSE_DEPTH
     float cT = 1.f, cz = 0.f, cw = 0.f;      // the compositing carries, across the passes
     int n_ran = 0;                           // P_g: the passes this workgroup ran
+#if NNR_PROPOSE_DEPTH == 2
+    bool found = false;                      // the ray's transmittance has fallen below a.level: the same value in every lane
+    float q = 0.f;                           // the depth at which it did
+#endif
 #else
     float* const s_raw = reinterpret_cast<float*>(smem + kRingF4 + kPark) + wave * (2 * kProposeMaxC);
     float* const s_z = s_raw + kProposeMaxC;
@@ -231,6 +249,19 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
         float excl = __shfl_up(incl, 1, 64);
         if (lane == 0) excl = 1.f;
         const float w = counted ? alpha * cT * excl : 0.f;
+#if NNR_PROPOSE_DEPTH == 2
+        {   // the first counted lane behind which the transmittance is below the level: list order is lane order, ballot then readlane
+#pragma clang fp contract(off)      // (this block: every operation of q is rounded on its own)
+            const float T0 = cT * excl, T1 = cT * incl;
+            const uint64_t who = __ballot(counted && T1 < a.level);      // (a NaN never crosses)
+            if (!found && who) {      // wave-uniform
+                const float ql = z + ((jn < C ? zn : z) - z) * ((T0 - a.level) / (T0 - T1));
+                const int src = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)who) - 1);
+                q = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ql), src));
+                found = true;
+            }
+        }
+#endif
         cT *= __shfl(incl, 31, 64);
         if (counted) { cz += w * z; cw += w; }
     }
@@ -252,10 +283,18 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
     if (live && lane0 == 0 && a.opt_passes) a.opt_passes[ray] = n_ran;
     {
         const float sz = wave_sum(cz), sw = wave_sum(cw);
+#if NNR_PROPOSE_DEPTH == 2
+        if (live && lane0 == 0) {      // no crossing: +inf, NaN where the carry is
+            a.out[3 * (int64_t)ray] = sz;
+            a.out[3 * (int64_t)ray + 1] = sw;
+            a.out[3 * (int64_t)ray + 2] = found ? q : (cT == cT ? __uint_as_float(0x7f800000u) : __uint_as_float(0x7fc00000u));
+        }
+#else
         if (live && lane0 == 0) {
             a.out[2 * (int64_t)ray] = sz;
             a.out[2 * (int64_t)ray + 1] = sw;
         }
+#endif
     }
 }
 #else      // ---- the proposal's staging and resampling stage ----
@@ -309,7 +348,11 @@ __global__ __launch_bounds__(256, 1) void NNR_PROPOSE_KERNEL(ProposeKernelArgs a
 #endif      // NNR_PROPOSE_DEPTH
 
 #if NNR_PROPOSE_DEPTH
+#if NNR_PROPOSE_DEPTH == 2
+hipError_t launch_render_depth_sparse_median(int D, const DepthSparseMedianArgs& a, hipStream_t st) {
+#else
 hipError_t launch_render_depth_sparse(int D, const DepthSparseArgs& a, hipStream_t st) {
+#endif
     if (a.R <= 0 || a.C < 1 || a.C > kProposeMaxC) return hipErrorInvalidValue;
 #elif NNR_PROPOSE_SPARSE
 hipError_t launch_propose_sparse(int D, const ProposeSparseArgs& a, hipStream_t st) {

@@ -1,13 +1,15 @@
 // nnr_sparse_api.cpp -- the extern "C" entry points of include/nnr_sparse.h (the sparse inference render) and include/nnr_sparse_stop.h (the same
 // render, stopped per workgroup once its rays are opaque): argument checking, shared, and marshalling into the kernels' argument structs
 // (nnr_sparse_kernels.h); of include/nnr_propose_sparse.h (the sparse proposal; nnr_propose_sparse_kernels.h) and of
-// include/nnr_depth_sparse.h (the sparse depth render; nnr_depth_sparse_kernels.h).  A host unit of its own, as nnr_fusion_api.cpp is.  Every error return is
+// include/nnr_depth_sparse.h (the sparse depth render; nnr_depth_sparse_kernels.h) and the sparse entry of include/nnr_depth_median.h (that
+// render with the quantile depth beside).  A host unit of its own, as nnr_fusion_api.cpp is.  Every error return is
 // decided before any device work -- no pointer is dereferenced here except the host arrays of the grid -- and the call is asynchronous on
 // the caller's stream.  No state: the last HIP error is nnr_api.cpp's (launched).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "../../include/nnr_depth_median.h"
 #include "../../include/nnr_depth_sparse.h"
 #include "../../include/nnr_propose_sparse.h"
 #include "../../include/nnr_sparse_stop.h"
@@ -139,6 +141,39 @@ int nnr_render_depth_sparse(const nnr_cfg* cfg, const float* pts_o, const float*
     a.t_min = t_min;
     a.flags = cfg->flags & (NNR_F_RELU_SIGMA | NNR_F_DIST_ALPHA);
     return launched(launch_render_depth_sparse(cfg->hidden, a, (hipStream_t)stream));
+}
+
+// the sparse depth render with the quantile depth (include/nnr_depth_median.h): nnr_render_depth_sparse's checks in their order; `level`
+// and t_min > level (the quantile would not be the unstopped one) are refused with the other bad values
+int nnr_render_depth_median_sparse(const nnr_cfg* cfg, const float* pts_o, const float* pts_d, const float* z_lo, const float* z_hi,
+                                   const float* jitter, const float grid_lo[3], const float grid_inv_step[3], const int32_t grid_dims[3],
+                                   const uint32_t* bits, float t_min, float level, const float* packed, float* out, float* opt_raw,
+                                   int32_t* opt_count, int32_t* opt_cell, int32_t* opt_passes, void* stream) {
+    if (!cfg || cfg->n_rays < 1 || cfg->n_samples < 1) return NNR_E_BADCFG;
+    if (!pts_o || !pts_d || !z_lo || !z_hi || !grid_lo || !grid_inv_step || !grid_dims || !bits || !packed || !out)
+        return NNR_E_BADCFG;      // (jitter and the opt_* may be null)
+    if (!(t_min >= 0.f && t_min < 1.f)) return NNR_E_BADCFG;      // (a NaN fails both comparisons)
+    if (!(level > 0.f && level < 1.f) || t_min > level) return NNR_E_BADCFG;
+    int64_t wx;
+    const int grid_rc = check_grid(grid_lo, grid_inv_step, grid_dims, &wx);
+    if (grid_rc == NNR_E_BADCFG) return grid_rc;
+    if (cfg->n_samples > 256 || (cfg->hidden != 128 && cfg->hidden != 256)) return NNR_E_UNSUPPORTED;
+    if ((cfg->flags & (NNR_F_BF16 | NNR_F_SPLIT3 | NNR_F_SPLIT2)) != (NNR_F_SPLIT3 | NNR_F_SPLIT2) || (cfg->flags & NNR_F_TRAIN)) return NNR_E_UNSUPPORTED;
+    if (grid_rc != NNR_OK) return grid_rc;
+    if (!aligned(packed, 16)) return NNR_E_ALIGN;
+    for (const void* p : {(const void*)pts_o, (const void*)pts_d, (const void*)z_lo, (const void*)z_hi, (const void*)jitter, (const void*)bits,
+                          (const void*)out, (const void*)opt_raw, (const void*)opt_count, (const void*)opt_cell, (const void*)opt_passes})
+        if (!aligned(p, 4)) return NNR_E_ALIGN;
+    DepthSparseMedianArgs a{};
+    a.pts_o = pts_o; a.pts_d = pts_d; a.z_lo = z_lo; a.z_hi = z_hi; a.jitter = jitter; a.bits = bits; a.packed = packed;
+    a.out = out; a.opt_raw = opt_raw; a.opt_count = opt_count; a.opt_cell = opt_cell; a.opt_passes = opt_passes;
+    for (int c = 0; c < 3; ++c) { a.lo[c] = grid_lo[c]; a.inv_step[c] = grid_inv_step[c]; a.n[c] = grid_dims[c]; }
+    a.wx = (int)wx;
+    a.R = cfg->n_rays; a.C = cfg->n_samples;
+    a.t_min = t_min;
+    a.flags = cfg->flags & (NNR_F_RELU_SIGMA | NNR_F_DIST_ALPHA);
+    a.level = level;
+    return launched(launch_render_depth_sparse_median(cfg->hidden, a, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -521,7 +521,37 @@ def projection_rows(camera_mat, world_mat, scale_mat=None):
     return (K @ W @ S)[:, :3, :].reshape(n, 12).to(torch.float32).contiguous()
 
 
-def render_depth_maps(renderer, camera_mat, world_mats, size, min_acc=0.5, chunk=1 << 18, scale_mat=None, occupancy=None, t_min=0.):
+def quantile_depth(alpha, z, level):
+    """The depth at which a ray's transmittance falls below `level`, from its per-sample alphas (R,C) and depths (R,C) or (C), in torch and in
+    the tensors' dtype: include/nnr_depth_median.h's definition with T as the cumulative product -- T_0 = 1, T_{i+1} = T_i (1 - alpha_i +
+    1e-6); m the first sample with T_{m+1} < level; q = z_m + (z_next - z_m) ((T_m - level) / (T_m - T_{m+1})), z_next = z_{m+1}, z_m
+    behind the last sample.  No crossing: +inf, NaN where the row's product is NaN."""
+    z = z.expand_as(alpha)
+    T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), (1. - alpha) + 1e-6], 1), 1)      # (R, C + 1)
+    crossed = T[:, 1:] < level
+    hit = crossed.any(1)
+    m = crossed.to(torch.int8).argmax(1, keepdim=True)                                            # (the first True)
+    z_m = z.gather(1, m)
+    z_n = z.gather(1, (m + 1).clamp(max=z.shape[1] - 1))
+    T0, T1 = T.gather(1, m), T.gather(1, m + 1)
+    q = (z_m + (z_n - z_m) * ((T0 - level) / (T0 - T1)))[:, 0]
+    none = torch.where(torch.isnan(T[:, -1]), torch.full_like(q, float('nan')), torch.full_like(q, float('inf')))
+    return torch.where(hit, q, none)
+
+
+def median_level(min_acc):
+    """The transmittance level of depth_mode 'median': fp32(1 - float64(min_acc)), as a Python float; 0 < min_acc < 1"""
+    min_acc = float(min_acc)
+    if not 0. < min_acc < 1.:      # (a NaN fails)
+        raise ValueError("depth_mode 'median': min_acc = %r must lie in (0, 1): the quantile of the ray's weight it asks for" % (min_acc,))
+    level = float(np.float32(1. - min_acc))
+    if not 0. < level < 1.:
+        raise ValueError("depth_mode 'median': min_acc = %r leaves no fp32 level in (0, 1)" % (min_acc,))
+    return level
+
+
+def render_depth_maps(renderer, camera_mat, world_mats, size, min_acc=0.5, chunk=1 << 18, scale_mat=None, occupancy=None, t_min=None,
+                      depth_mode='expected'):
     """The z-depth maps of renderer.model seen from the cameras (camera_mat, world_mats[i]) -> (n, H, W) fp32 on the model's device: what
     nope_nerf(eval_=True) reports as depth, without its colour.  Rays come from nnr.camera.ray_setup on arange_pixels((H, W)), the samples
     from the renderer's own z tables without noise; the rendered distance is divided by ray_norm under rendering.normalise_ray.
@@ -531,18 +561,31 @@ def render_depth_maps(renderer, camera_mat, world_mats, size, min_acc=0.5, chunk
     occupancy: an OccupancyGrid of this (frozen) field, the caller's to keep valid.  With it and C <= 256 every chunk goes through the sparse
     depth kernel (nnr.ops.render_depth_sparse: samples in cells the grid calls empty are not evaluated, a workgroup of four rays stops once
     each is below the transmittance t_min); with C > 256 the grid is ignored and one logged line says so.  A culled sample is absent from
-    the product, so the maps are the dense ones only as far as the grid's alpha_min is negligible.  t_min (0 <= t_min < 1; 0: off; a
+    the product, so the maps are the dense ones only as far as the grid's alpha_min is negligible.  t_min (0 <= t_min < 1; 0 or None: off; a
     ValueError without a grid): stopping drops weight and never adds any, it lowers a ray's acc by less than
     t_min (1 + C 1e-6 (1 + 1e-6)^C), about t_min, and moves its depth by at most that times the far depth.  Next to min_acc: a pixel whose
     full acc lies within that margin above min_acc can turn +inf, none turns finite; keep t_min well below min_acc (1e-3 against 0.5).
     min_acc, normalise_ray and the +inf rule are the same with and without a grid.
+    depth_mode 'expected': all of the above.  'median' (DESIGN.md section 11.4): the pixel is q, the depth at which the ray's transmittance
+    falls below level = fp32(1 - min_acc) -- where its accumulated weight reaches min_acc; 0 < min_acc < 1 --, divided by ray_norm as the
+    depth is; +inf where it never does (the same event as `observed`), NaN stays NaN.  It lies on a surface the ray crosses, and the stop
+    does not move it: with a grid t_min None means level (a smaller t_min is kept, a larger one is a ValueError), and the maps are
+    bit for bit those of t_min = 0.  Above 256 samples quantile_depth of render_rays' alphas.
     sample_option 'ndc': NotImplementedError -- NDC depths are not world depths.  GPU only."""
     import nnr
     from nnr import camera as _camera
     from .common import arange_pixels
+    if depth_mode not in ('expected', 'median'):
+        raise ValueError("render_depth_maps: depth_mode %r is neither 'expected' nor 'median'" % (depth_mode,))
+    median = depth_mode == 'median'
+    level = median_level(min_acc) if median else None
+    if t_min is None:      # expected: off; median: stop at the level, where a grid makes the stop available
+        t_min = level if median and occupancy is not None else 0.
     t_min = float(t_min)
     if occupancy is None and t_min != 0.:
         raise ValueError("render_depth_maps: t_min = %r stops rays in the sparse depth kernel alone, which needs `occupancy`" % (t_min,))
+    if median and float(np.float32(t_min)) > level:
+        raise ValueError("render_depth_maps: t_min = %r above the median mode's level %r: a ray stopped there has not crossed it" % (t_min, level))
     cfg, net = renderer.cfg, renderer.model
     if cfg['sample_option'] == 'ndc':
         raise NotImplementedError("render_depth_maps: rendering.sample_option 'ndc' samples in NDC space, whose depths are not world depths")
@@ -574,6 +617,19 @@ def render_depth_maps(renderer, camera_mat, world_mats, size, min_acc=0.5, chunk
             origin, ray, view, ray_norm, _, _ = _camera.ray_setup(pixels, None, K, world_mats[i:i + 1], S, normalise, use_dir)
             for r0 in range(0, H * W, int(chunk)):
                 sl = slice(r0, min(r0 + int(chunk), H * W))
+                if median:
+                    if n_samples <= 256 and occupancy is not None:
+                        q = _nnr_ops.render_depth_sparse(origin[sl], ray[sl], z_lo, z_hi, None, occupancy, w, b, hidden=net.hidden_dim,
+                                                         dist_alpha=dist_alpha, relu_sigma=relu_sigma, t_min=t_min, quantile_level=level)[:, 2]
+                    elif n_samples <= 256:
+                        q = _nnr_ops.render_depth(origin[sl], ray[sl], z_lo, z_hi, None, w, b, hidden=net.hidden_dim, dist_alpha=dist_alpha,
+                                                  relu_sigma=relu_sigma, quantile_level=level)[:, 2]
+                    else:
+                        _, _, alpha, _ = nnr.render_rays(origin[sl], ray[sl], view[sl], z_lo, z_hi, None, w, b, hidden=net.hidden_dim,
+                                                         dist_alpha=dist_alpha, white_bg=False, relu_sigma=relu_sigma, samples=True)
+                        q = quantile_depth(alpha, z_lo, level)
+                    out[i, sl] = q / ray_norm[sl] if normalise else q
+                    continue
                 if n_samples <= 256 and occupancy is not None:
                     da = _nnr_ops.render_depth_sparse(origin[sl], ray[sl], z_lo, z_hi, None, occupancy, w, b, hidden=net.hidden_dim,
                                                       dist_alpha=dist_alpha, relu_sigma=relu_sigma, t_min=t_min)
@@ -639,7 +695,7 @@ def _dense_from_bricks(values, dims):
 
 
 def extract_mesh_tsdf(renderer, cameras, lo, hi, resolution, refine=None, trunc_voxels=3, dilate=1, colour=True, integrate=None,
-                      depth_maps=None, min_acc=0.5, chunk=65536, max_bricks=None, occupancy=None, t_min=0.):
+                      depth_maps=None, min_acc=0.5, chunk=65536, max_bricks=None, occupancy=None, t_min=None, depth_mode='expected'):
     """The zero set of the truncated signed distance volume fused from the model's rendered depth maps of `cameras` (a Cameras) inside the box
     [lo, hi], as a Mesh at level 0 (Curless-Levoy with weight 1 per observation): what the model was trained on -- the rendered depth of
     its learned cameras -- and not a level of the raw density.  `inside` (positive) is behind the surfaces the cameras saw.
@@ -653,7 +709,8 @@ def extract_mesh_tsdf(renderer, cameras, lo, hi, resolution, refine=None, trunc_
                     volume is truncated at trunc_voxels coarse steps, the fine bricks at trunc_voxels fine steps.
       depth_maps    (n,H,W) z-depth maps on the integrator's device where the caller has them, or a callable () -> such maps (a timer's
                     hook); None: render_depth_maps(renderer, ...) with min_acc, occupancy and t_min (an OccupancyGrid of the frozen field
-                    and the stop's transmittance: the sparse depth kernel, see there).
+                    and the stop's transmittance: the sparse depth kernel, see there) and depth_mode ('expected', or 'median': the
+                    depth at which the ray's accumulated weight reaches min_acc; with it t_min None stops at that level).
       integrate     a callable (origin, step, bricks, cams, depth, trunc, sum, weight) that stands in for nnr.ops.tsdf_integrate (the CPU
                     tests' reference integrator, a timer's hook); with it and depth_maps the host side runs anywhere, normals and colours
                     are then made only where a renderer on the GPU is given as well.
@@ -669,8 +726,12 @@ def extract_mesh_tsdf(renderer, cameras, lo, hi, resolution, refine=None, trunc_
         integrate = lambda o, s, br, cm, dp, tr, sm, wt: _nnr_ops.tsdf_integrate(o, s, br, cm, dp, tr, sm, wt)
     with torch.no_grad():
         if depth_maps is None:
-            depth = render_depth_maps(renderer, cameras.camera_mat, cameras.world_mats, cameras.size, min_acc=min_acc, scale_mat=cameras.scale_mat,
-                                      occupancy=occupancy, t_min=t_min)
+            if depth_mode == 'expected':
+                depth = render_depth_maps(renderer, cameras.camera_mat, cameras.world_mats, cameras.size, min_acc=min_acc,
+                                          scale_mat=cameras.scale_mat, occupancy=occupancy, t_min=t_min)
+            else:
+                depth = render_depth_maps(renderer, cameras.camera_mat, cameras.world_mats, cameras.size, min_acc=min_acc,
+                                          scale_mat=cameras.scale_mat, occupancy=occupancy, t_min=t_min, depth_mode=depth_mode)
         else:
             depth = depth_maps() if callable(depth_maps) else depth_maps
         depth = depth.detach().to(torch.float32).contiguous()

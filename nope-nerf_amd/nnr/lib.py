@@ -81,6 +81,8 @@ SPARSE_STOP_EXPORTS = ("nnr_render_sparse_stop",)
 PROPOSE_SPARSE_EXPORTS = ("nnr_propose_sparse",)
 #: include/nnr_depth_sparse.h: the depth render that skips the samples a grid calls empty and stops once its rays are opaque, also under ABI 8
 DEPTH_SPARSE_EXPORTS = ("nnr_render_depth_sparse",)
+#: include/nnr_depth_median.h: the two depth renders with the quantile (median) depth beside depth and acc, also under ABI 8
+DEPTH_MEDIAN_EXPORTS = ("nnr_render_depth_median", "nnr_render_depth_median_sparse")
 #: include/nnr_regularise.h: the ray-distortion regulariser on the compositing weights, also under ABI 8
 REGULARISE_EXPORTS = ("nnr_ray_distortion_fwd", "nnr_ray_distortion_bwd")
 #: include/nnr_frozen.h: the frozen-field render (ray gradients only, no stash, no weight gradient), also under ABI 8
@@ -208,6 +210,8 @@ def load():
     lib.nnr_render_sparse_stop.argtypes = [cfgp] + [vp] * 6 + [C.POINTER(f32), C.POINTER(f32), C.POINTER(i32)] + [vp] * 2 + [f32] + [vp] * 6
     lib.nnr_propose_sparse.argtypes = [cfgp, i32] + [vp] * 6 + [C.POINTER(f32), C.POINTER(f32), C.POINTER(i32)] + [vp] * 10
     lib.nnr_render_depth_sparse.argtypes = [cfgp] + [vp] * 5 + [C.POINTER(f32), C.POINTER(f32), C.POINTER(i32)] + [vp, f32] + [vp] * 7
+    lib.nnr_render_depth_median.argtypes = [cfgp] + [vp] * 5 + [f32] + [vp] * 5
+    lib.nnr_render_depth_median_sparse.argtypes = [cfgp] + [vp] * 5 + [C.POINTER(f32), C.POINTER(f32), C.POINTER(i32)] + [vp, f32, f32] + [vp] * 7
     lib.nnr_ray_distortion_fwd.argtypes = [cfgp, vp, i32, vp, f32, f32, vp, vp]
     lib.nnr_ray_distortion_bwd.argtypes = [cfgp, vp, i32, vp, f32, f32, vp, vp, i32, i32, vp]
     lib.nnr_frozen_workspace_floats.restype = C.c_size_t
@@ -224,7 +228,7 @@ def load():
     lib.nnr_frozen_sparse_bwd.argtypes = [cfgp] + [vp] * 8
     lib.nnr_prof_begin.argtypes = [i32]
     lib.nnr_prof_end.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-    for n in (EXPORTS + GEOMETRY_EXPORTS + FUSION_EXPORTS + SPARSE_EXPORTS + SPARSE_STOP_EXPORTS + PROPOSE_SPARSE_EXPORTS + DEPTH_SPARSE_EXPORTS + REGULARISE_EXPORTS
+    for n in (EXPORTS + GEOMETRY_EXPORTS + FUSION_EXPORTS + SPARSE_EXPORTS + SPARSE_STOP_EXPORTS + PROPOSE_SPARSE_EXPORTS + DEPTH_SPARSE_EXPORTS + DEPTH_MEDIAN_EXPORTS + REGULARISE_EXPORTS
               + FROZEN_EXPORTS + FROZEN_SPARSE_EXPORTS):
         if not hasattr(lib, n):
             raise RuntimeError(f"libnnr.so does not export {n}")

@@ -723,13 +723,27 @@ def density_bricks(origin, step, bricks: torch.Tensor, weights, biases, *, hidde
     return out
 
 
+def _quantile_level(level, what):
+    """quantile_level of the depth renders: None, or a float the fp32 of which lies in (0, 1)"""
+    if level is None:
+        return None
+    level = float(level)
+    if not 0.0 < C.c_float(level).value < 1.0:      # (a NaN fails)
+        raise ValueError("%s: quantile_level must be in (0, 1); got %r" % (what, level))
+    return level
+
+
 def render_depth(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor, jitter: Optional[torch.Tensor], weights, biases, *,
-                 hidden: int, dist_alpha: bool, relu_sigma: bool, debug: bool = False):
+                 hidden: int, dist_alpha: bool, relu_sigma: bool, debug: bool = False, quantile_level: Optional[float] = None):
     """The rendered depth of rays from the density alone in one launch of nnr_render_depth (include/nnr_fusion.h): the inputs of a render_rays
     call without the view direction -> (R,2) fp32, (depth, acc) per ray: depth = sum w_j z_j and acc = sum w_j over the compositor's weights.
     No colour branch, nothing per sample written to HBM.  Always in the two-term fp16 products (split2_cfg), with the cached pack, as propose.
     (NaN, NaN) for a ray with a NaN sample.  debug: (out, raw (R,C), z (R,C)), the samples' raw densities and depths.  1 <= C <= 256.
+    quantile_level (None: the call above): a float in (0, 1) -> (R,3), (depth, acc, q) in one launch of nnr_render_depth_median
+    (include/nnr_depth_median.h): q the depth at which the ray's transmittance falls below the level (0.5: the median depth), +inf where it
+    never does; depth and acc are bit for bit the two columns above.
     Not differentiable.  No host synchronisation."""
+    level = _quantile_level(quantile_level, "render_depth")
     _require_gpu(pts_o)
     R, Cn = pts_o.shape[0], z_lo.shape[0]
     dev = pts_o.device
@@ -737,10 +751,14 @@ def render_depth(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z
     (pts_o, pts_d), z_lo, z_hi, jit = _ray_inputs((pts_o, pts_d), z_lo, z_hi, jitter)
     packed = _packed_for(cfg, list(weights), list(biases))
     f32 = dict(dtype=torch.float32, device=dev)
-    out = torch.empty(R, 2, **f32)
+    out = torch.empty(R, 2 if level is None else 3, **f32)
     raw, zv = (torch.empty(R, Cn, **f32), torch.empty(R, Cn, **f32)) if debug else (None, None)
-    L.check(L.load().nnr_render_depth(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), L.ptr(packed), L.ptr(out),
-                                      L.ptr(raw), L.ptr(zv), L.stream()), "nnr_render_depth")
+    if level is None:
+        L.check(L.load().nnr_render_depth(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), L.ptr(packed), L.ptr(out),
+                                          L.ptr(raw), L.ptr(zv), L.stream()), "nnr_render_depth")
+    else:
+        L.check(L.load().nnr_render_depth_median(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), level,
+                                                 L.ptr(packed), L.ptr(out), L.ptr(raw), L.ptr(zv), L.stream()), "nnr_render_depth_median")
     return (out, raw, zv) if debug else out
 
 
@@ -954,17 +972,26 @@ depth_sparse_tally = None      # tools: while this is a list, every render_depth
 
 
 def render_depth_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Tensor, z_hi: torch.Tensor, jitter: Optional[torch.Tensor], grid,
-                        weights, biases, *, hidden: int, dist_alpha: bool, relu_sigma: bool, t_min: float = 0.0, debug: bool = False):
+                        weights, biases, *, hidden: int, dist_alpha: bool, relu_sigma: bool, t_min: float = 0.0, debug: bool = False,
+                        quantile_level: Optional[float] = None):
     """render_depth that does not evaluate the samples an occupancy grid calls empty and stops a workgroup of four rays once they are opaque,
     in one launch of nnr_render_depth_sparse (include/nnr_depth_sparse.h): render_depth's inputs plus `grid`, as render_sparse takes it ->
     (R,2) fp32, (depth, acc) per ray over the evaluated samples -- bit for bit the dist and acc render_sparse(..., t_min=t_min) gives the
     same rays, without its colour branch, view direction and rgb.  A ray without a live sample gets (0, 0); a culled or unevaluated sample
     cannot make its ray NaN.  t_min (0 <= t_min < 1; 0: the full lists run): as render_sparse's.  The cached pack, as propose.
     debug: (out, raw (R,C) pre-filled with NaN and written at the evaluated samples alone, count (R) int32, cell (R,C) int32, passes (R)
-    int32).  Any R, 1 <= C <= 256.  Not differentiable.  No host synchronisation."""
+    int32).  Any R, 1 <= C <= 256.
+    quantile_level (None: the call above): a float in (0, 1), t_min <= quantile_level -> (R,3), (depth, acc, q) in one launch of
+    nnr_render_depth_median_sparse (include/nnr_depth_median.h): q the depth at which the transmittance over the evaluated samples falls
+    below the level, +inf where it never does -- the same bits at every t_min up to the level; everything else is the call above's bit
+    for bit at the same t_min.
+    Not differentiable.  No host synchronisation."""
     t_min = float(t_min)
     if not 0.0 <= t_min < 1.0:      # (a NaN fails)
         raise ValueError("render_depth_sparse: t_min must be in [0, 1); got %r" % (t_min,))
+    level = _quantile_level(quantile_level, "render_depth_sparse")
+    if level is not None and C.c_float(t_min).value > C.c_float(level).value:
+        raise ValueError("render_depth_sparse: t_min = %r above quantile_level = %r: a ray stopped there has not crossed the level" % (t_min, level))
     _require_gpu(pts_o)
     R, Cn = pts_o.shape[0], z_lo.shape[0]
     dev = pts_o.device
@@ -972,7 +999,7 @@ def render_depth_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Te
     (pts_o, pts_d), z_lo, z_hi, jit = _ray_inputs((pts_o, pts_d), z_lo, z_hi, jitter)
     lo3, is3, d3, bits = _grid_args(grid, dev, "render_depth_sparse")
     packed = _packed_for(cfg, list(weights), list(biases))
-    out = torch.empty(R, 2, dtype=torch.float32, device=dev)
+    out = torch.empty(R, 2 if level is None else 3, dtype=torch.float32, device=dev)
     raw = count = cell = passes = None
     if debug:
         raw = torch.full((R, Cn), float("nan"), dtype=torch.float32, device=dev)
@@ -981,9 +1008,14 @@ def render_depth_sparse(pts_o: torch.Tensor, pts_d: torch.Tensor, z_lo: torch.Te
     tally = depth_sparse_tally
     if tally is not None and not debug:
         count, passes = torch.empty(R, dtype=torch.int32, device=dev), torch.empty(R, dtype=torch.int32, device=dev)
-    L.check(L.load().nnr_render_depth_sparse(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), lo3, is3, d3,
-                                             L.ptr(bits), t_min, L.ptr(packed), L.ptr(out), L.ptr(raw), L.ptr(count), L.ptr(cell),
-                                             L.ptr(passes), L.stream()), "nnr_render_depth_sparse")
+    if level is None:
+        L.check(L.load().nnr_render_depth_sparse(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), lo3, is3, d3,
+                                                 L.ptr(bits), t_min, L.ptr(packed), L.ptr(out), L.ptr(raw), L.ptr(count), L.ptr(cell),
+                                                 L.ptr(passes), L.stream()), "nnr_render_depth_sparse")
+    else:
+        L.check(L.load().nnr_render_depth_median_sparse(C.byref(cfg), L.ptr(pts_o), L.ptr(pts_d), L.ptr(z_lo), L.ptr(z_hi), L.ptr(jit), lo3, is3,
+                                                        d3, L.ptr(bits), t_min, level, L.ptr(packed), L.ptr(out), L.ptr(raw), L.ptr(count),
+                                                        L.ptr(cell), L.ptr(passes), L.stream()), "nnr_render_depth_median_sparse")
     if tally is not None:
         tally.append((count.sum(), passes.sum(), R * Cn, R))
     return (out, raw, count, cell, passes) if debug else out

@@ -91,6 +91,8 @@ def tsdf(args, G, renderer, cfg, scalars, lo, hi):
     n_cams, (H, W) = cams.world_mats.shape[0], cams.size
     G.render_depth_maps(renderer, cams.camera_mat, cams.world_mats[:1], (2, 2))      # loads the code object, packs the weights
     grid, t_min = None, 0. if args.t_min is None else args.t_min
+    median = args.depth_mode == "median"      # the maps stop at the level (render_depth_maps' default with a grid); --t-min is the expected mode's
+    maps = {}
     if args.occupancy is not None:
         occ = {"resolution": int(args.occupancy[0]), "alpha_min": float(args.occupancy[1]), "dilate": args.occupancy_dilate}
         if args.occupancy_bounds is not None:
@@ -100,6 +102,8 @@ def tsdf(args, G, renderer, cfg, scalars, lo, hi):
         if grid is None:
             sys.exit("extract_mesh: rendering.occupancy %r gives no grid for this config (see the logged reason)" % (occ,))
         first = occupancy_report(G, ops, renderer, cams, grid, t_min, args.min_acc)
+        if median:
+            first_median = median_passes_report(G, ops, renderer, cams, grid, args.min_acc)
     torch.cuda.synchronize()
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
@@ -108,8 +112,12 @@ def tsdf(args, G, renderer, cfg, scalars, lo, hi):
 
     def depth_maps():
         render_ev[0].record()
-        d = G.render_depth_maps(renderer, cams.camera_mat, cams.world_mats, (H, W), min_acc=args.min_acc, occupancy=grid, t_min=t_min)
+        if median:
+            d = G.render_depth_maps(renderer, cams.camera_mat, cams.world_mats, (H, W), min_acc=args.min_acc, occupancy=grid, depth_mode="median")
+        else:
+            d = G.render_depth_maps(renderer, cams.camera_mat, cams.world_mats, (H, W), min_acc=args.min_acc, occupancy=grid, t_min=t_min)
         render_ev[1].record()
+        maps["depth"] = d
         return d
 
     def integrate(o, s, br, cm, dp, tr, sm, wt):
@@ -133,9 +141,15 @@ def tsdf(args, G, renderer, cfg, scalars, lo, hi):
     print("checkpoint: it %s" % scalars.get('it', '?'))
     print("cameras: %d of %d x %d (every %d), %d samples per ray, min acc %g" % (n_cams, H, W, args.every, samples, args.min_acc))
     print("depth renders: %.3f ms (%.3f ns per sample)%s" % (ms_r, ms_r * 1e6 / (n_cams * H * W * samples),
-                                                           "" if grid is None else ", sparse depth kernel, t_min %g" % t_min))
+                                                           "" if grid is None else ", sparse depth kernel, t_min %g"
+                                                           % (G.median_level(args.min_acc) if median else t_min)))
+    if median:
+        print("depth mode: median (level %g), %.4f %% of the pixels finite" % (G.median_level(args.min_acc),
+                                                                            100. * float(torch.isfinite(maps["depth"]).float().mean())))
     if grid is not None:
         print("occupancy: %s, first frame: %s" % (occ, first))
+        if median:
+            print("median mode, first frame: %s; expected mode at t_min %g: %s passes" % (first_median, t_min, first.get("passes_run")))
     print("fusion: %d launches, %.3f ms (%.4f ns per voxel-camera pair), truncation %g voxels" % (len(fuse_ev), ms_f, ms_f * 1e6 / max(1, pairs[0]),
                                                                                             args.trunc_voxels))
     print("grid: %d x %d x %d in [%s] .. [%s]%s, %d bricks" % (tuple(mesh.dims) + (", ".join("%g" % v for v in lo), ", ".join("%g" % v for v in hi),
@@ -165,6 +179,24 @@ def check_occupancy_args(ap, args):
             ap.error("--occupancy-dilate N: a cell count >= 0")
     if args.t_min is not None and not 0. < args.t_min < 1.:
         ap.error("--t-min T lies in (0, 1)")
+    if args.depth_mode != "expected" and args.method != "tsdf":
+        ap.error("--depth-mode: with --method tsdf only")
+    if args.depth_mode == "median" and not 0. < args.min_acc < 1.:
+        ap.error("--depth-mode median: --min-acc lies in (0, 1), the quantile of the ray's weight")
+
+
+def median_passes_report(G, ops, renderer, cams, grid, min_acc):
+    """The first fused frame in median mode, stopped at its level -> the mean passes a ray's workgroup ran"""
+    ops.depth_sparse_tally = []
+    try:
+        G.render_depth_maps(renderer, cams.camera_mat, cams.world_mats[:1], cams.size, min_acc=min_acc, occupancy=grid, depth_mode="median")
+        tally = ops.depth_sparse_tally
+    finally:
+        ops.depth_sparse_tally = None
+    res = {"t_min": G.median_level(min_acc)}
+    if tally:      # (none above 256 samples per ray: the dense render ran)
+        res["passes_run"] = round(sum(float(t[1]) for t in tally) / sum(t[3] for t in tally), 4)
+    return res
 
 
 def occupancy_report(G, ops, renderer, cams, grid, t_min, min_acc):
@@ -216,6 +248,10 @@ def main():
                     help="with --occupancy: the grid's box on every axis (default: the cube of rendering.radius)")
     ap.add_argument("--t-min", type=float, default=None, metavar="T",
                     help="with --occupancy: stop a workgroup of four rays once each is below this transmittance, 0 < T < 1")
+    ap.add_argument("--depth-mode", choices=("expected", "median"), default="expected",
+                    help="with --method tsdf: fuse the expected depth sum w z (default) or the depth at which a ray's accumulated weight "
+                         "reaches --min-acc (the median at 0.5); with --occupancy the median maps stop at that level, --t-min is then the "
+                         "expected mode's in the report")
     args = ap.parse_args()
     check_occupancy_args(ap, args)
     if not torch.cuda.is_available():
